@@ -6,17 +6,20 @@ iterations per ray), 3 fields x 3 index columns, 1024 x 1024 pupil per bundle, F
 113,246,208 ray-surface intersections per step.  A step = ONE launch of the trace kernel over that batch in
 history mode — the API-faithful output of `raytrace(surfaces, y, x, U, V, Vector{RealRay})` (reference
 src/PupilSampling.jl:34-65): x and y on every surface, 16 B written per intersection; rays are generated on the
-device from the bundle axes (0 B read per ray); inputs resident in HBM.  Beside the headline the same run
-measures: the other arithmetic policy, a sustained figure over >= 1 s of launches, summary mode, BASELINE
-config 3 (aspheric, 2048^2 pupil) through full_trace with the stop-filter compaction, an oracle check of a
-strided sample of the timed kernel's output, and the CPU baseline.
+device from the bundle axes (0 B read per ray); inputs resident in HBM.  A plain run does what that figure
+needs and no more: setup, the best-placed pair of output arrays, >= 1 s of launches back to back (the clocks
+the timed steps are meant to see; reported as `sustained`), W warm-up + K timed steps, the result line;
+`--dump-outputs DIR` writes what the last timed step computed.  With `--full` the same run also measures:
+the layout's store ceiling, the other arithmetic policy, summary mode, BASELINE config 3 (aspheric, 2048^2
+pupil) through full_trace with the stop-filter compaction, configs 5, 4 and 1, an oracle check of a strided
+sample of the timed kernel's output, and the CPU baseline (at N > 1: the exchange leg below).
 
 N > 1: the SAME workload and metric under WEAK scaling — the path shards over independent (system, field, index column,
 pupil row) units (src/PupilSampling.jl:34-65 is a pure function of its arguments), so rank r traces its own instance of
 the batch (zoom position r of the same Double-Gauss: the same 9 bundles x 1024^2 rays x S = 12) with NO collective in the
 data path; the K steps are bracketed by a barrier + synchronize on both sides, the slowest rank's time counts, `value` =
 N x 113,246,208 x K / that time.  One curve over N = 1, 2, 4, 8 is therefore one workload.
-The exchange step north_star names — reassembling the image-plane hits of a sharded sweep — is measured in the same run
+The exchange step north_star names — reassembling the image-plane hits of a sharded sweep — is measured in a `--full` run
 and reported under `extra.config4_allgather` (BASELINE.json configs[3]): zoom-lens sweep, 32 positions x 5 index columns
 x 5 fields x 512^2 pupil = 209,715,200 rays, 2.52e9 intersections per step, STRONG scaling: the 800 bundles are split
 into contiguous rank-ordered slabs, every rank traces its slab in summary mode into a packed [2][n] hit slab, and ONE
@@ -129,6 +132,37 @@ def verify_sample(pres, bundles, axes, k, xv, yv, policy: str, stride: int = 409
     return {"verified": bool(ok), "sample_rays": int(idx.size), "sample": f"every {stride}th ray of the last timed launch's history, all {gx.shape[0]} surfaces",
             "checker": "oracle/ort_oracle.c (CPU)", "bit_identical": bool(exact), "max_rel_deviation": worst,
             "nan_pattern_mismatches": pat, "bar": "bit-identical" if policy == "ieee" else "<= 1e-10 relative, NaN patterns identical"}
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, torch, per_ray, whole=None, valid=None, seed=20240229):
+    """--dump-outputs: what the timed path left on the device -> `dirname`/<name>.npy.  `per_ray`: {name: tensor whose last axis
+    runs over the same n rays}; `whole`: {name: small tensor written as it is}.  Float32 and Float64 are kept, any other type is
+    written as Float64.  If all of it is more than 64 MB, the per-ray arrays are cut to one seeded, sorted sample of their last
+    axis: the same sample for the same shapes, whatever the build.  `valid`: [rows] — the entries of each row of a 2-D slab that
+    the call defines (ort_full_trace_*: count[b]); what lies behind them is memory the call never wrote, dumped as 0."""
+    import numpy as np
+    whole = whole or {}
+    os.makedirs(dirname, exist_ok=True)
+    width = lambda t: 4 if t.dtype == torch.float32 else 8
+    n = next(iter(per_ray.values())).shape[-1]
+    col_bytes = sum(t.numel() // n * width(t) for t in per_ray.values())
+    room = DUMP_MAX_BYTES - sum(t.numel() * width(t) for t in whole.values()) - 256 * (len(per_ray) + len(whole))   # (.npy headers)
+    idx = None
+    if n * col_bytes > room:
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=room // col_bytes, replace=False))
+    for name, t in {**per_ray, **whole}.items():
+        if idx is not None and name in per_ray:
+            t = t.index_select(t.dim() - 1, torch.from_numpy(idx).to(t.device))
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if valid is not None and name in per_ray:
+            cols = np.arange(n) if idx is None else idx
+            a = np.where(cols[None, :] >= valid[:, None], a.dtype.type(0), a)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def timed_launches(eng, fn, steps: int, warmup: int = 2, preroll_s: float = 0.0):
@@ -285,9 +319,18 @@ def bench_single(args, torch, rank, world, local_rank, emit=True):
     achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
     value = world * inter * args.steps / wall
 
+    if args.dump_outputs and rank == 0:                     # what the last timed step left, before anything else launches
+        if args.mode == "history":
+            dump_outputs(args.dump_outputs, torch, {"xv": xv, "yv": yv})
+        elif args.mode == "summary":
+            dump_outputs(args.dump_outputs, torch, {"xf": xf, "yf": yf, "xs": xs, "ys": ys, "status": st})
+        else:
+            dump_outputs(args.dump_outputs, torch, {"ex": ex, "ey": ey, "rho": rho, "theta": th}, whole={"count": cnt, "rms": rms},
+                         valid=cnt.cpu().numpy())
+
     # ---- correctness of what was just timed: a strided sample of the history against the CPU oracle ----
     verify = None
-    if args.mode == "history" and not args.no_verify:
+    if args.full and args.mode == "history" and not args.no_verify:
         try:
             verify = verify_sample(pres, bundles, axes, k, xv, yv, args.policy)
         except Exception as exc:                                # noqa: BLE001 — reported as not verified, never hidden
@@ -301,7 +344,7 @@ def bench_single(args, torch, rank, world, local_rank, emit=True):
 
     # ---- the other arithmetic policy, same launch, reported beside the headline ----
     other = None
-    if args.mode != "full_trace" and world == 1:
+    if args.full and args.mode != "full_trace" and world == 1:
         ofl = (fl & ~_capi.ORT_FAST_MATH) if fast else (fl | _capi.ORT_FAST_MATH)
         ostep = grid_step(out, ofl)
         osus = None
@@ -721,7 +764,7 @@ def bench_single(args, torch, rank, world, local_rank, emit=True):
         return extra
 
     extra = {}
-    if not args.no_extras and args.mode == "history" and world == 1:
+    if args.full and not args.no_extras and args.mode == "history" and world == 1:
         try:
             extra = run_extras()
         except Exception as exc:                                # noqa: BLE001 — the headline line must still be printed
@@ -795,7 +838,7 @@ def bench_single(args, torch, rank, world, local_rank, emit=True):
         res["single_rank_same_workload_value"] = inter / (per_rank[0] * 1e-3)
         res["roofline"]["note"] = "per GPU: rank 0's kernel, hipEvents on its launch stream"
         res["backend"] = backend
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         try:
             res["cpu_baseline"] = cpu_baseline(api, pres, bundles, axes, k)
             res["cpu_baseline"]["gpu_over_cpu_1core"] = value / res["cpu_baseline"]["value"]
@@ -953,6 +996,8 @@ def bench_multi(args, torch, rank, world, local_rank, emit=True, headline=None):
 
     run(args.warmup, True)
     wall = run(args.steps, True)                                # the timed region: trace + all-gather, overlapped
+    if args.dump_outputs and rank == 0:                         # the sweep's hits as the last timed step reassembled them
+        dump_outputs(args.dump_outputs, torch, {"hits": gathered[(args.steps - 1) & 1]})
     wall_trace = run(args.steps, False)                         # gather-exclusive
     # the all-gather alone
     sync_all()
@@ -1186,8 +1231,16 @@ def main():
     ap.add_argument("--policy", default="fast", choices=["fast", "ieee"],
                     help="arithmetic policy of the timed kernel: fast = direction-cosine form (<= 1e-10 relative, status exact; "
                          "anomalous waves retrace with the reference sequence); ieee = the reference's IEEE operation sequence "
-                         "(bit-identical to the CPU oracle).  The other policy is timed too and reported beside it.")
+                         "(bit-identical to the CPU oracle).  With --full the other policy is timed too and reported beside it.")
     ap.add_argument("--fast-math", action="store_true", help="alias of --policy fast")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also run what a plain run leaves out: the layout store ceiling, the oracle check of the "
+                         "timed output, the other arithmetic policy, the extras (summary, configs 3, 5, 4, 1; at N > 1 the exchange "
+                         "leg) and the CPU baseline.  The --no-* options below drop single legs of it.  --workload config4 / config5 "
+                         "is that leg alone with its own checks, with or without --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed as DIR/<name>.npy (float64 / float32; of an output "
+                         "larger than 64 MB in all a fixed, seeded sample of rays)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the summary / config-3 extras")
     ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of the timed output")
@@ -1224,7 +1277,7 @@ def main():
     # shape and stores, no ray tracing)?  Run as a child process BEFORE this process touches the GPU.
     args.layout_ceiling = None
     exe = os.path.join(ROOT, "tools", "store_ceiling")
-    if world == 1 and args.workload in ("auto", "config2") and not args.no_ceiling and os.path.exists(exe):
+    if args.full and world == 1 and args.workload in ("auto", "config2") and not args.no_ceiling and os.path.exists(exe):
         try:
             import subprocess
             runs = []
@@ -1244,7 +1297,7 @@ def main():
         # N > 1: the headline workload under weak scaling, then the exchange step (config 4 + all-gather) as an extra of the line
         res = bench_single(args, torch, rank, world, local_rank, emit=False)
         leg = None
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             try:
                 leg = bench_multi(args, torch, rank, world, local_rank, emit=False, headline=res)
             except Exception as exc:                            # noqa: BLE001 — the headline line must still be printed

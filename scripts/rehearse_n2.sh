@@ -6,6 +6,7 @@
 # the ranks itself: scripts/final_profile.sh rehearses that form.)
 cd /root/repo
 export ORT_BENCH_BACKEND=gloo
-timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 --zoom 4 --pupil4 256 > gpurun_out/rehearse_n2.log 2>&1
-echo "rc=$?" >> gpurun_out/rehearse_n2.log
-tail -c 2500 gpurun_out/rehearse_n2.log
+LOG=${1:-/tmp/rehearse_n2.log}
+timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 --zoom 4 --pupil4 256 --full > $LOG 2>&1
+echo "rc=$?" >> $LOG
+tail -c 2500 $LOG

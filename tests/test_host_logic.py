@@ -161,3 +161,34 @@ def test_best_placed_keeps_the_fastest_candidate():
     made.clear()
     chosen, rep = best_placed(make, time_ms, candidates=1)
     assert chosen == 0 and rep["candidates_ms"] == [] and len(made) == 1
+
+
+def test_bench_dump_outputs_is_a_fixed_sample_within_its_budget(tmp_path):
+    """bench.py --dump-outputs: Float64 / Float32 .npy files of every output; past the byte budget all per-ray arrays are cut to
+    ONE sorted sample of rays that a second call reproduces; entries behind a slab row's count are written as 0."""
+    import importlib.util
+    import os
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    assert bench.DUMP_MAX_BYTES <= 64 * 10 ** 6
+    bench.DUMP_MAX_BYTES = 20000
+    n = 5003
+    xv = torch.arange(3 * n, dtype=torch.float64).reshape(3, n)
+    st = (torch.arange(n) % 7).to(torch.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch, {"xv": xv, "status": st}, whole={"rms": torch.ones(4, dtype=torch.float32)})
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["rms.npy", "status.npy", "xv.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in got) <= 20000
+    assert all(np.array_equal(a, np.load(tmp_path / "b" / f)) for f, a in got.items())
+    assert got["xv.npy"].dtype == np.float64 and got["status.npy"].dtype == np.float64 and got["rms.npy"].dtype == np.float32
+    idx = got["xv.npy"][0].astype(np.int64)                          # row 0 of xv holds the ray index itself
+    assert 400 < idx.size < n and (np.diff(idx) > 0).all()
+    assert np.array_equal(got["xv.npy"][2], idx + 2.0 * n) and np.array_equal(got["status.npy"], idx % 7)
+    bench.DUMP_MAX_BYTES = 64 * 10 ** 6                              # small outputs are written whole; counts mask the slab rows
+    ex = torch.full((3, 10), 2.5, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "c"), torch, {"ex": ex}, whole={"count": torch.tensor([4, 10, 0])}, valid=np.array([4, 10, 0]))
+    e = np.load(tmp_path / "c" / "ex.npy")
+    assert e.shape == (3, 10) and (e != 0).sum(axis=1).tolist() == [4, 10, 0] and np.load(tmp_path / "c" / "count.npy").tolist() == [4.0, 10.0, 0.0]
