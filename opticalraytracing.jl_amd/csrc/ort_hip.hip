@@ -69,19 +69,10 @@ constexpr int kSmallGridTiles = 256;  // full_trace launches of at most this man
                                       // 8 waves per tile on 1024 SIMDs — beyond two waves per SIMD the two-ray form's lower instruction count wins
 constexpr size_t kZeroCopyBytes = (size_t)1 << 20;   // spot pipelines whose packed block [inputs | results] is at most this large run on the
                                                      // pinned host block directly (no copy dispatches)
-#ifndef ORT_WALK_TARGET
-#define ORT_WALK_TARGET 16384
-#endif
-#ifndef ORT_FUSE_MARGIN
-#define ORT_FUSE_MARGIN 4096
-#endif
-#ifndef ORT_FUSE_SCAN_LAG
-#define ORT_FUSE_SCAN_LAG 1024
-#endif
-constexpr int kFuseMargin = ORT_FUSE_MARGIN;     // fused full_trace: workgroups between a bundle's last tile and the first placement of its tiles
-constexpr int kFuseScanLag = ORT_FUSE_SCAN_LAG;  // ... and the workgroup that runs the bundle's scan (every tile's workgroup has long been dispatched by then)
+constexpr int kFuseMargin = 4096;   // fused full_trace: workgroups between a bundle's last tile and the first placement of its tiles
+constexpr int kFuseScanLag = 1024;  // ... and the workgroup that runs the bundle's scan (every tile's workgroup has long been dispatched by then)
 static_assert(kFuseScanLag <= kFuseMargin, "the scan runs ahead of the placements");
-constexpr int64_t kWalkTargetGroups = ORT_WALK_TARGET;   // statistics-only walk route: workgroups a launch is cut into when it has that many spans
+constexpr int64_t kWalkTargetGroups = 16384;   // statistics-only walk route: workgroups a launch is cut into when it has that many spans
                                                // (~8 per resident slot of the chip); fewer spans: one workgroup per span
 constexpr int kSmallPairs = 256;    // spot pipelines of at most this many (system, field) pairs prepare in one launch (k_small_prepare)
 constexpr size_t kPackedVectorBytes = 32u << 20;   // host callers: error vectors up to this size come back in ONE copy
@@ -287,9 +278,27 @@ int make_rb_slopes(ort_ctx* ctx, TraceParams<T>& p, int nb)
     return ORT_OK;
 }
 
+// zeroed launch parameters that point at the tables of a system batch
+template <typename T>
+TraceParams<T> system_params(const ort_system* sys)
+{
+    TraceParams<T> p;
+    memset(&p, 0, sizeof p);
+    p.recs = Sel<T>::rec(sys); p.polys = Sel<T>::poly(sys); p.arms = Sel<T>::arms(sys); p.S = sys->rows - 1; p.apert2 = Sel<T>::ap2(sys);
+    return p;
+}
+
+// the grid source's shape: ny x nx rays per bundle in tiles of kTile
+template <typename T>
+void set_grid_shape(TraceParams<T>& p, int ny, int nx, unsigned flags)
+{
+    p.ny = ny; p.nx = nx; p.rpb = (int64_t)ny * nx; p.tiles_per_bundle = (int)((p.rpb + kTile - 1) / kTile);
+    p.raybasis = (flags & ORT_RAYBASIS) ? 1 : 0;
+}
+
 template <typename T>
 int upload_bundles(ort_ctx* ctx, const ort_system* sys, int nb, const ort_bundle* bundles, int ny, int nx,
-                   int64_t axes_len, unsigned flags, const DevBundle<T>** dev)
+                   int64_t axes_len, const DevBundle<T>** dev)
 {
     std::vector<DevBundle<T>> hb((size_t)nb);
     const int S = sys->rows - 1;
@@ -318,7 +327,6 @@ int upload_bundles(ort_ctx* ctx, const ort_system* sys, int nb, const ort_bundle
         d.xoff = s.xaxis_off;
         hb[b] = d;
     }
-    (void)flags;
     const size_t bytes = hb.size() * sizeof(DevBundle<T>);
     const unsigned char* raw = reinterpret_cast<const unsigned char*>(hb.data());
     const bool same = ctx->bundle_cache.size() == bytes && ctx->slot[SL_BUNDLES].p &&
@@ -353,12 +361,9 @@ int trace_grid_impl(ort_ctx* ctx, const ort_system* sys, int nb, const ort_bundl
     if ((out->xs || out->ys)) for (int b = 0; b < nb; ++b) if (bundles[b].stop <= 0) return fail(ORT_EINVAL, "xs/ys requested but bundle %d has no stop", b);
     const bool devp = flags & ORT_DEVICE_PTRS;
 
-    TraceParams<T> p;
-    memset(&p, 0, sizeof p);
-    p.recs = Sel<T>::rec(sys); p.polys = Sel<T>::poly(sys); p.arms = Sel<T>::arms(sys); p.S = S; p.apert2 = Sel<T>::ap2(sys);
-    rc = upload_bundles<T>(ctx, sys, nb, bundles, ny, nx, axes_len, flags, &p.bundles); if (rc) return rc;
-    p.ny = ny; p.nx = nx; p.rpb = rpb; p.tiles_per_bundle = (int)((rpb + kTile - 1) / kTile);
-    p.raybasis = (flags & ORT_RAYBASIS) ? 1 : 0;
+    TraceParams<T> p = system_params<T>(sys);
+    rc = upload_bundles<T>(ctx, sys, nb, bundles, ny, nx, axes_len, &p.bundles); if (rc) return rc;
+    set_grid_shape(p, ny, nx, flags);
     const int64_t blocks = (int64_t)nb * p.tiles_per_bundle;
 
     if (devp) {
@@ -423,9 +428,7 @@ int trace_list_impl(ort_ctx* ctx, const ort_system* sys, int isys, int64_t nrays
     const bool summ = status != nullptr;
     if (!hist && !summ) return fail(ORT_EINVAL, "no output requested");
     if (hist && ld < nrays) return fail(ORT_EINVAL, "ld %lld < rays %lld", (long long)ld, (long long)nrays);
-    TraceParams<T> p;
-    memset(&p, 0, sizeof p);
-    p.recs = Sel<T>::rec(sys); p.polys = Sel<T>::poly(sys); p.arms = Sel<T>::arms(sys); p.S = S; p.apert2 = Sel<T>::ap2(sys);
+    TraceParams<T> p = system_params<T>(sys);
     p.nrays = nrays; p.isys = isys; p.slopes_given = (flags & ORT_INPUT_SLOPES) ? 1 : 0;
     const int64_t blocks = (nrays + kTile - 1) / kTile;
     if (flags & ORT_DEVICE_PTRS) {
@@ -463,9 +466,168 @@ static unsigned next_ft_epoch(ort_ctx* ctx)
     return ctx->ft_epoch;
 }
 
-// The full_trace stages on a prepared TraceParams (recs / coefs / bundles / axes / grid shape set by the
-// caller): tile buffers, trace with the FT epilogue, scan + scatter + finalize (or the statistics-only
-// merge), results to the caller.  ex == NULL selects statistics only.
+// Arms the in-launch hand-offs of a full_trace launch (fused and look-back routes): a new epoch for its ready / look-back words
+// and a cleared fault word
+template <typename T>
+int arm_handoff(ort_ctx* ctx, TraceParams<T>& p)
+{
+    p.ft_epoch = next_ft_epoch(ctx);
+    int rc = dev_out<int>(ctx, SL_FTERR, 1, &p.ft_err); if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(p.ft_err, 0, sizeof(int), ctx->stream));
+    return ORT_OK;
+}
+
+// The full_trace routes, one function each.  They run on the TraceParams run_full_trace has prepared (tile aggregates included) and
+// leave count / rms — and, all but the statistics walk, the survivors in ex / ey / rho / theta [nb][2*rpb] — in DEVICE memory.
+
+// Statistics only, one pass: trace + stop filter + per-tile (n, mean, M2), merged per bundle — no ray-sized buffer at all
+template <typename T>
+int ft_stats_walk(ort_ctx* ctx, TraceParams<T>& p, int nb, size_t npart, int64_t* count, double* rms, unsigned flags)
+{
+    int rc = dev_out<double>(ctx, SL_TOFF, npart, &p.tile_m2x); if (rc) return rc;
+    rc = dev_out<double>(ctx, SL_TSQ, npart, &p.tile_m2y); if (rc) return rc;
+    // ONE route (k_trace, FT_WALK): a workgroup walks spans of tiles of its bundle, four partials (one per wave) per span.
+    // The span length is a function of the BUNDLE's shape alone — one tile for bundles of a few tiles (the reference's
+    // own call), kWalkTiles beyond — so a bundle's statistics never depend on what else is in the launch; how many
+    // consecutive spans a workgroup walks (walk_group) is a launch-shape choice that no result depends on: as many as
+    // leave the launch ~8 workgroups per resident slot, down to ONE tile per workgroup for a call of a few tiles
+    // (latency: 4 workgroups for the reference's own 2,048 rays)
+    const int span = p.tiles_per_bundle <= kSmallTiles ? 1 : kWalkTiles;
+    p.walk_spans = (p.tiles_per_bundle + span - 1) / span;
+    const int parts = p.walk_spans * (kBlock / 64);             // (n, mean, M2) partials per bundle
+    const int64_t spans = (int64_t)nb * p.walk_spans;
+    p.walk_group = (int)std::min<int64_t>(p.walk_spans, std::max<int64_t>(1, spans / kWalkTargetGroups));
+    const int groups = (p.walk_spans + p.walk_group - 1) / p.walk_group;
+    rc = span == 1 ? launch_trace<T, true, false, false, FT_WALK1>(ctx, p, (int64_t)nb * groups, flags)
+                   : launch_trace<T, true, false, false, FT_WALK>(ctx, p, (int64_t)nb * groups, flags);
+    if (rc) return rc;
+    if (parts <= 64 && !(flags & ORT_NO_SMALL_PATH))           // one wave per bundle: the same merges in the same order (bit-identical)
+        hipLaunchKernelGGL(k_ft_stats_reduce_wave, dim3((unsigned)((nb + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, ctx->stream,
+                           p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_m2x, p.tile_m2y, p.tile_rmax, parts, nb, count, rms);
+    else
+        hipLaunchKernelGGL(k_ft_stats_reduce, dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
+                           p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_m2x, p.tile_m2y, p.tile_rmax, parts, count, rms);
+    HIP_TRY(hipGetLastError());
+    return ORT_OK;
+}
+
+// workspace of the two-pass and fused routes: a slot of kTile entries per tile for its compacted survivors (p.out_*) + the tile offsets
+template <typename T>
+int ft_workspace(ort_ctx* ctx, TraceParams<T>& p, int64_t tiles, int64_t** tile_off)
+{
+    const size_t nw = (size_t)tiles * kTile;
+    int rc = dev_out<T>(ctx, SL_WEX, nw, &p.out_ex); if (rc) return rc;
+    rc = dev_out<T>(ctx, SL_WEY, nw, &p.out_ey); if (rc) return rc;
+    rc = dev_out<T>(ctx, SL_WR, nw, &p.out_r); if (rc) return rc;
+    rc = dev_out<T>(ctx, SL_WTH, nw, &p.out_th); if (rc) return rc;
+    return dev_out<int64_t>(ctx, SL_TOFF, (size_t)tiles, tile_off);
+}
+
+// Default route: tile-local compaction into a workspace | tile offsets + bundle aggregates | placement of the survivors in both
+// halves + squared deviations | sigma.  No workgroup waits for another.
+template <typename T>
+int ft_two_pass(ort_ctx* ctx, TraceParams<T>& p, int nb, bool small_f64, double* chunk_sq, FtBundleAgg* agg,
+                T* ex, T* ey, T* rho, T* theta, int64_t* count, double* rms, unsigned flags)
+{
+    const int64_t tiles = (int64_t)nb * p.tiles_per_bundle;
+    int64_t* tile_off;
+    int rc = ft_workspace<T>(ctx, p, tiles, &tile_off); if (rc) return rc;
+    if (small_f64) rc = launch_trace<T, true, false, false, FT_FULL, sizeof(T) == 8 ? 1 : kRPT>(ctx, p, tiles, flags);
+    else rc = launch_trace<T, true, false, false, FT_FULL>(ctx, p, tiles, flags);
+    if (rc) return rc;
+    if (p.tiles_per_bundle <= kSmallTiles && !(flags & ORT_NO_SMALL_PATH)) {
+        // bundles of a few tiles (the reference's own call: 4): offsets, placement and sigma by one workgroup per bundle
+        // in ONE launch, through the same bodies (k_ft_small_finish)
+        hipLaunchKernelGGL((k_ft_small_finish<T>), dim3((unsigned)nb), dim3(kBlock * kFinishGroups), 0, ctx->stream,
+                           p.out_ex, p.out_ey, p.out_r, p.out_th, p.rpb, p.tiles_per_bundle, p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_rmax, tile_off, agg,
+                           ex, ey, rho, theta, chunk_sq, count, rms);
+        HIP_TRY(hipGetLastError());
+        return ORT_OK;
+    }
+    hipLaunchKernelGGL(k_ft_scan, dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
+                       p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_rmax, p.tiles_per_bundle, tile_off, agg);
+    HIP_TRY(hipGetLastError());
+    const int64_t pgroups = (int64_t)nb * ((p.tiles_per_bundle + kPlaceTiles - 1) / kPlaceTiles);   // kPlaceTiles tiles per workgroup
+    hipLaunchKernelGGL((k_ft_place<T>), dim3((unsigned)pgroups), dim3(kBlock), 0, ctx->stream,
+                       p.out_ex, p.out_ey, p.out_r, p.out_th, p.rpb, p.tiles_per_bundle, p.tile_cnt, tile_off, agg, ex, ey, rho, theta, chunk_sq);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((k_ft_finalize<1>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
+                       chunk_sq, p.tiles_per_bundle, agg, count, rms, (const int*)p.ft_err);
+    HIP_TRY(hipGetLastError());
+    return ORT_OK;
+}
+
+// ORT_FT_FUSED: the default route (ft_two_pass) with the second pass inside the trace launch (k_trace, FT_FUSED):
+// workgroup i traces tile i and places tile i - lag
+template <typename T>
+int ft_fused(ort_ctx* ctx, TraceParams<T>& p, int nb, double* chunk_sq, FtBundleAgg* agg,
+             T* ex, T* ey, T* rho, T* theta, int64_t* count, double* rms, unsigned flags)
+{
+    const int64_t tiles = (int64_t)nb * p.tiles_per_bundle;
+    int rc = ft_workspace<T>(ctx, p, tiles, &p.tile_off); if (rc) return rc;
+    rc = dev_out<int>(ctx, SL_FTDONE, (size_t)nb + 4, &p.ft_done); if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(p.ft_done, 0, ((size_t)nb * sizeof(int) + 15) & ~(size_t)15, ctx->stream));   // arrivals are counted within the call
+    rc = arm_handoff(ctx, p); if (rc) return rc;
+    rc = dev_out<unsigned>(ctx, SL_FTREADY, (size_t)nb, &p.ft_ready); if (rc) return rc;
+    if (ctx->slot[SL_FTREADY].cap != ctx->ft_ready_cap) {
+        HIP_TRY(hipMemsetAsync(p.ft_ready, 0, ctx->slot[SL_FTREADY].cap, ctx->stream));
+        ctx->ft_ready_cap = ctx->slot[SL_FTREADY].cap;
+    }
+    p.agg = agg; p.tile_sq = chunk_sq;                           // (a partial per wave)
+    p.fin_ex = ex; p.fin_ey = ey; p.fin_rho = rho; p.fin_th = theta;
+    p.fuse_ntiles = (int)tiles;
+    p.fuse_lag = p.tiles_per_bundle + kFuseMargin;
+    p.fuse_scan_lag = kFuseScanLag;
+    p.fuse_spin_cap = 1 << 22;
+    if (ctx->test_fused_no_scan) {                               // testing aid: nobody runs the scans, the waits give up early
+        p.fuse_scan_lag = 0x3fffffff; p.fuse_spin_cap = 1 << 10;
+    }
+    if (tiles + p.fuse_lag > 0x7fffffffLL) return fail(ORT_EINVAL, "launch too large");
+    rc = launch_trace<T, true, false, false, FT_FUSED>(ctx, p, tiles + p.fuse_lag, flags); if (rc) return rc;
+    hipLaunchKernelGGL((k_ft_finalize<kBlock / 64>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
+                       chunk_sq, p.tiles_per_bundle, agg, count, rms, (const int*)p.ft_err);
+    HIP_TRY(hipGetLastError());
+    return ORT_OK;
+}
+
+// ORT_FT_LOOKBACK: the trace kernel writes the first half itself.  Look-back state: one 8-byte word per tile + the ticket
+// counter; zero-filled when (re)allocated only — the epoch tells the words of this launch from older ones, the base does the
+// same for tickets
+template <typename T>
+int ft_lookback(ort_ctx* ctx, TraceParams<T>& p, int nb, double* chunk_sq, FtBundleAgg* agg,
+                T* ex, T* ey, T* rho, T* theta, int64_t* count, double* rms, unsigned flags)
+{
+    const int64_t tiles = (int64_t)nb * p.tiles_per_bundle;
+    int rc = arm_handoff(ctx, p); if (rc) return rc;
+    rc = dev_out<unsigned long long>(ctx, SL_FTSTATE, (size_t)tiles, &p.ft_state); if (rc) return rc;
+    if (ctx->slot[SL_FTSTATE].cap != ctx->ft_state_cap) {
+        HIP_TRY(hipMemsetAsync(p.ft_state, 0, ctx->slot[SL_FTSTATE].cap, ctx->stream));
+        ctx->ft_state_cap = ctx->slot[SL_FTSTATE].cap;
+    }
+    if (!ctx->slot[SL_FTTICKET].p) {
+        rc = dev_out<unsigned long long>(ctx, SL_FTTICKET, 1, &p.ft_ticket); if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(p.ft_ticket, 0, sizeof(unsigned long long), ctx->stream));
+        ctx->ft_ticket_base = 0;
+    }
+    p.ft_ticket = static_cast<unsigned long long*>(ctx->slot[SL_FTTICKET].p);
+    p.ft_ticket_base = ctx->ft_ticket_base;
+    p.out_ex = ex; p.out_ey = ey; p.out_r = rho; p.out_th = theta;
+    rc = launch_trace<T, true, false, false, FT_LOOKBACK>(ctx, p, tiles, flags); if (rc) return rc;
+    ctx->ft_ticket_base += (unsigned long long)tiles;            // only a launch that went out has taken its tickets
+    hipLaunchKernelGGL(k_ft_scan, dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
+                       p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_rmax, p.tiles_per_bundle, (int64_t*)nullptr, agg);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((k_ft_mirror<T>), dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream,
+                       p.rpb, p.tiles_per_bundle, agg, ex, ey, rho, theta, chunk_sq, (const int*)p.ft_err);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL((k_ft_finalize<1>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
+                       chunk_sq, p.tiles_per_bundle, agg, count, rms, (const int*)p.ft_err);
+    HIP_TRY(hipGetLastError());
+    return ORT_OK;
+}
+
+// The full_trace stages on a prepared TraceParams (recs / coefs / bundles / axes / grid shape set by the caller): what the
+// routes share — tile buffers, device outputs, the route choice, results to the caller.  ex == NULL selects statistics only.
 template <typename T>
 int run_full_trace(ort_ctx* ctx, TraceParams<T>& p, int nb, T* ex, T* ey, T* rho, T* theta,
                    int64_t* count, double* rms, unsigned flags)
@@ -475,11 +637,7 @@ int run_full_trace(ort_ctx* ctx, TraceParams<T>& p, int nb, T* ex, T* ey, T* rho
     const int64_t rpb = p.rpb, N = rpb * nb;
     const int64_t tiles = (int64_t)nb * p.tiles_per_bundle;
     if (tiles > 0x7fffffffLL) return fail(ORT_EINVAL, "launch too large");
-#ifndef ORT_POLY_RPT1
-#define ORT_POLY_RPT1 0
-#endif
-    const bool small_f64 = sizeof(T) == 8 && ((p.tiles_per_bundle <= kSmallTiles && tiles <= kSmallGridTiles && !(flags & ORT_NO_SMALL_PATH)) ||
-                                              (ORT_POLY_RPT1 && p.arms >= ARMS_EVEN));
+    const bool small_f64 = sizeof(T) == 8 && p.tiles_per_bundle <= kSmallTiles && tiles <= kSmallGridTiles && !(flags & ORT_NO_SMALL_PATH);
     int rc;
     // per-tile aggregates — or, on the statistics-only walk route, four partials per span (of one tile at the least)
     const size_t npart = (size_t)tiles * (stats_only ? kBlock / 64 : 1);
@@ -492,167 +650,45 @@ int run_full_trace(ort_ctx* ctx, TraceParams<T>& p, int nb, T* ex, T* ey, T* rho
         rc = dev_out<int64_t>(ctx, SL_RES0, (size_t)nb, &dcount); if (rc) return rc;
         rc = dev_out<double>(ctx, SL_RES1, (size_t)nb, &drms); if (rc) return rc;
     }
-    if (stats_only) {
-        // one pass: trace + stop filter + per-tile (n, mean, M2), merged per bundle — no ray-sized buffer at all
-        rc = dev_out<double>(ctx, SL_TOFF, npart, &p.tile_m2x); if (rc) return rc;
-        rc = dev_out<double>(ctx, SL_TSQ, npart, &p.tile_m2y); if (rc) return rc;
-        // ONE route (k_trace, FT_WALK): a workgroup walks spans of tiles of its bundle, four partials (one per wave) per span.
-        // The span length is a function of the BUNDLE's shape alone — one tile for bundles of a few tiles (the reference's
-        // own call), kWalkTiles beyond — so a bundle's statistics never depend on what else is in the launch; how many
-        // consecutive spans a workgroup walks (walk_group) is a launch-shape choice that no result depends on: as many as
-        // leave the launch ~8 workgroups per resident slot, down to ONE tile per workgroup for a call of a few tiles
-        // (latency: 4 workgroups for the reference's own 2,048 rays)
-        const int span = p.tiles_per_bundle <= kSmallTiles ? 1 : kWalkTiles;
-        p.walk_spans = (p.tiles_per_bundle + span - 1) / span;
-        const int parts = p.walk_spans * (kBlock / 64);             // (n, mean, M2) partials per bundle
-        const int64_t spans = (int64_t)nb * p.walk_spans;
-        p.walk_group = (int)std::min<int64_t>(p.walk_spans, std::max<int64_t>(1, spans / kWalkTargetGroups));
-        const int groups = (p.walk_spans + p.walk_group - 1) / p.walk_group;
-        rc = span == 1 ? launch_trace<T, true, false, false, FT_WALK1>(ctx, p, (int64_t)nb * groups, flags)
-                       : launch_trace<T, true, false, false, FT_WALK>(ctx, p, (int64_t)nb * groups, flags);
-        if (rc) return rc;
-        if (parts <= 64 && !(flags & ORT_NO_SMALL_PATH))           // one wave per bundle: the same merges in the same order (bit-identical)
-            hipLaunchKernelGGL(k_ft_stats_reduce_wave, dim3((unsigned)((nb + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, ctx->stream,
-                               p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_m2x, p.tile_m2y, p.tile_rmax, parts, nb, dcount, drms);
-        else
-            hipLaunchKernelGGL(k_ft_stats_reduce, dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
-                               p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_m2x, p.tile_m2y, p.tile_rmax, parts, dcount, drms);
-        HIP_TRY(hipGetLastError());
-        if (!devp) {
-            rc = from_device<int64_t>(ctx, count, dcount, (size_t)nb); if (rc) return rc;
-            rc = from_device<double>(ctx, rms, drms, (size_t)nb); if (rc) return rc;
-            HIP_TRY(hipStreamSynchronize(ctx->stream));
-        }
-        return ORT_OK;
-    }
-    double* chunk_sq; FtBundleAgg* agg; int* ft_err = nullptr; bool fused_finish = false;
-    rc = dev_out<double>(ctx, SL_TSQ, (size_t)tiles * (kBlock / 64), &chunk_sq); if (rc) return rc;   // (fused route: a partial per wave)
-    rc = dev_out<FtBundleAgg>(ctx, SL_AGG, (size_t)nb, &agg); if (rc) return rc;
     T *dex = ex, *dey = ey, *drho = rho, *dth = theta;
-    if (!devp) {
-        rc = dev_out<T>(ctx, SL_OUT0, (size_t)2 * N, &dex); if (rc) return rc;
-        rc = dev_out<T>(ctx, SL_OUT1, (size_t)2 * N, &dey); if (rc) return rc;
-        rc = dev_out<T>(ctx, SL_OUT2, (size_t)2 * N, &drho); if (rc) return rc;
-        rc = dev_out<T>(ctx, SL_OUT4, (size_t)2 * N, &dth); if (rc) return rc;
-    }
-    if (!(flags & ORT_FT_LOOKBACK)) {
-        // default route: tile-local compaction into a workspace | tile offsets + bundle aggregates | placement of the
-        // survivors in both halves + squared deviations | sigma.  No workgroup waits for another.
-        T *wex, *wey, *wr, *wth; int64_t* tile_off;
-        const size_t nw = (size_t)tiles * kTile;                 // a slot of kTile entries per tile
-        rc = dev_out<T>(ctx, SL_WEX, nw, &wex); if (rc) return rc;
-        rc = dev_out<T>(ctx, SL_WEY, nw, &wey); if (rc) return rc;
-        rc = dev_out<T>(ctx, SL_WR, nw, &wr); if (rc) return rc;
-        rc = dev_out<T>(ctx, SL_WTH, nw, &wth); if (rc) return rc;
-        rc = dev_out<int64_t>(ctx, SL_TOFF, (size_t)tiles, &tile_off); if (rc) return rc;
-        p.out_ex = wex; p.out_ey = wey; p.out_r = wr; p.out_th = wth;
+    if (stats_only) rc = ft_stats_walk<T>(ctx, p, nb, npart, dcount, drms, flags);
+    else {
+        double* chunk_sq; FtBundleAgg* agg;
+        rc = dev_out<double>(ctx, SL_TSQ, (size_t)tiles * (kBlock / 64), &chunk_sq); if (rc) return rc;   // (fused route: a partial per wave)
+        rc = dev_out<FtBundleAgg>(ctx, SL_AGG, (size_t)nb, &agg); if (rc) return rc;
+        if (!devp) {
+            rc = dev_out<T>(ctx, SL_OUT0, (size_t)2 * N, &dex); if (rc) return rc;
+            rc = dev_out<T>(ctx, SL_OUT1, (size_t)2 * N, &dey); if (rc) return rc;
+            rc = dev_out<T>(ctx, SL_OUT2, (size_t)2 * N, &drho); if (rc) return rc;
+            rc = dev_out<T>(ctx, SL_OUT4, (size_t)2 * N, &dth); if (rc) return rc;
+        }
         const bool fused = (flags & ORT_FT_FUSED) && nb >= 2 && p.tiles_per_bundle > kSmallTiles && !small_f64;
-        if (fused) {
-            // the second pass inside the trace launch (k_trace, FT_FUSED): workgroup i traces tile i and places tile i - lag
-            rc = dev_out<int>(ctx, SL_FTDONE, (size_t)nb + 4, &p.ft_done); if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(p.ft_done, 0, ((size_t)nb * sizeof(int) + 15) & ~(size_t)15, ctx->stream));   // arrivals are counted within the call
-            p.ft_epoch = next_ft_epoch(ctx);
-            rc = dev_out<unsigned>(ctx, SL_FTREADY, (size_t)nb, &p.ft_ready); if (rc) return rc;
-            if (ctx->slot[SL_FTREADY].cap != ctx->ft_ready_cap) {
-                HIP_TRY(hipMemsetAsync(p.ft_ready, 0, ctx->slot[SL_FTREADY].cap, ctx->stream));
-                ctx->ft_ready_cap = ctx->slot[SL_FTREADY].cap;
-            }
-            rc = dev_out<int>(ctx, SL_FTERR, 1, &p.ft_err); if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(p.ft_err, 0, sizeof(int), ctx->stream));
-            ft_err = p.ft_err;
-            p.tile_off = tile_off; p.agg = agg; p.tile_sq = chunk_sq;
-            p.fin_ex = dex; p.fin_ey = dey; p.fin_rho = drho; p.fin_th = dth;
-            p.fuse_ntiles = (int)tiles;
-            p.fuse_lag = p.tiles_per_bundle + kFuseMargin;
-            p.fuse_scan_lag = kFuseScanLag;
-            p.fuse_spin_cap = 1 << 22;
-            if (ctx->test_fused_no_scan) {                           // testing aid: nobody runs the scans, the waits give up early
-                p.fuse_scan_lag = 0x3fffffff; p.fuse_spin_cap = 1 << 10;
-            }
-            if (tiles + p.fuse_lag > 0x7fffffffLL) return fail(ORT_EINVAL, "launch too large");
-            rc = launch_trace<T, true, false, false, FT_FUSED>(ctx, p, tiles + p.fuse_lag, flags); if (rc) return rc;
-        } else
-        if (small_f64) rc = launch_trace<T, true, false, false, FT_FULL, sizeof(T) == 8 ? 1 : kRPT>(ctx, p, tiles, flags);
-        else rc = launch_trace<T, true, false, false, FT_FULL>(ctx, p, tiles, flags);
-        if (rc) return rc;
-        if (fused) {
-            hipLaunchKernelGGL((k_ft_finalize<kBlock / 64>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
-                               chunk_sq, p.tiles_per_bundle, agg, dcount, drms, (const int*)ft_err);
-            HIP_TRY(hipGetLastError());
-            fused_finish = true;
-        } else
-        if (p.tiles_per_bundle <= kSmallTiles && !(flags & ORT_NO_SMALL_PATH)) {
-            // bundles of a few tiles (the reference's own call: 4): offsets, placement and sigma by one workgroup per bundle
-            // in ONE launch, through the same bodies (k_ft_small_finish)
-            hipLaunchKernelGGL((k_ft_small_finish<T>), dim3((unsigned)nb), dim3(kBlock * kFinishGroups), 0, ctx->stream,
-                               wex, wey, wr, wth, rpb, p.tiles_per_bundle, p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_rmax, tile_off, agg,
-                               dex, dey, drho, dth, chunk_sq, dcount, drms);
-            HIP_TRY(hipGetLastError());
-            fused_finish = true;
-        } else {
-            hipLaunchKernelGGL(k_ft_scan, dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
-                               p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_rmax, p.tiles_per_bundle, tile_off, agg);
-            HIP_TRY(hipGetLastError());
-            const int64_t pgroups = (int64_t)nb * ((p.tiles_per_bundle + kPlaceTiles - 1) / kPlaceTiles);   // kPlaceTiles tiles per workgroup
-            hipLaunchKernelGGL((k_ft_place<T>), dim3((unsigned)pgroups), dim3(kBlock), 0, ctx->stream,
-                               wex, wey, wr, wth, rpb, p.tiles_per_bundle, p.tile_cnt, tile_off, agg, dex, dey, drho, dth, chunk_sq);
-            HIP_TRY(hipGetLastError());
-        }
-    } else {
-        // ORT_FT_LOOKBACK: the trace kernel writes the first half itself.  Look-back state: one 8-byte word per tile +
-        // the ticket counter; zero-filled when (re)allocated only — the epoch tells the words of this launch from
-        // older ones, the base does the same for tickets
-        p.ft_epoch = next_ft_epoch(ctx);
-        rc = dev_out<unsigned long long>(ctx, SL_FTSTATE, (size_t)tiles, &p.ft_state); if (rc) return rc;
-        if (ctx->slot[SL_FTSTATE].cap != ctx->ft_state_cap) {
-            HIP_TRY(hipMemsetAsync(p.ft_state, 0, ctx->slot[SL_FTSTATE].cap, ctx->stream));
-            ctx->ft_state_cap = ctx->slot[SL_FTSTATE].cap;
-        }
-        if (!ctx->slot[SL_FTTICKET].p) {
-            rc = dev_out<unsigned long long>(ctx, SL_FTTICKET, 1, &p.ft_ticket); if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(p.ft_ticket, 0, sizeof(unsigned long long), ctx->stream));
-            ctx->ft_ticket_base = 0;
-        }
-        p.ft_ticket = static_cast<unsigned long long*>(ctx->slot[SL_FTTICKET].p);
-        rc = dev_out<int>(ctx, SL_FTERR, 1, &p.ft_err); if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(p.ft_err, 0, sizeof(int), ctx->stream));
-        ft_err = p.ft_err;
-        p.ft_ticket_base = ctx->ft_ticket_base;
-        p.out_ex = dex; p.out_ey = dey; p.out_r = drho; p.out_th = dth;
-        rc = launch_trace<T, true, false, false, FT_LOOKBACK>(ctx, p, tiles, flags); if (rc) return rc;
-        ctx->ft_ticket_base += (unsigned long long)tiles;        // only a launch that went out has taken its tickets
-        hipLaunchKernelGGL(k_ft_scan, dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
-                           p.tile_cnt, p.tile_sx, p.tile_sy, p.tile_rmax, p.tiles_per_bundle, (int64_t*)nullptr, agg);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL((k_ft_mirror<T>), dim3((unsigned)tiles), dim3(kBlock), 0, ctx->stream,
-                           rpb, p.tiles_per_bundle, agg, dex, dey, drho, dth, chunk_sq, (const int*)ft_err);
-        HIP_TRY(hipGetLastError());
+        if (!(flags & ORT_FT_LOOKBACK))
+            rc = fused ? ft_fused<T>(ctx, p, nb, chunk_sq, agg, dex, dey, drho, dth, dcount, drms, flags)
+                       : ft_two_pass<T>(ctx, p, nb, small_f64, chunk_sq, agg, dex, dey, drho, dth, dcount, drms, flags);
+        else rc = ft_lookback<T>(ctx, p, nb, chunk_sq, agg, dex, dey, drho, dth, dcount, drms, flags);
     }
-    if (!fused_finish) {
-        hipLaunchKernelGGL((k_ft_finalize<1>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream,
-                           chunk_sq, p.tiles_per_bundle, agg, dcount, drms, (const int*)ft_err);
-        HIP_TRY(hipGetLastError());
+    // the one host return path: count / rms, the fault word, the valid entries of every bundle
+    if (rc || devp) return rc;
+    int herr = 0;
+    rc = from_device<int64_t>(ctx, count, dcount, (size_t)nb); if (rc) return rc;
+    rc = from_device<double>(ctx, rms, drms, (size_t)nb); if (rc) return rc;
+    if (p.ft_err) { rc = from_device<int>(ctx, &herr, p.ft_err, 1); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (herr)
+        return fail(ORT_EHIP, "full_trace in-launch hand-off fault (%s): the survivors' offsets are not trustworthy, nothing was returned",
+                    (herr & 2) ? "tile tickets outside the launch: the context's ticket base and the device counter disagree"
+                               : "a workgroup waited for its predecessors beyond the poll cap");
+    if (stats_only) return ORT_OK;
+    for (int b = 0; b < nb; ++b) {
+        const size_t off = (size_t)b * 2 * rpb, cnt = (size_t)count[b];
+        if (!cnt) continue;
+        rc = from_device<T>(ctx, ex + off, dex + off, cnt); if (rc) return rc;
+        rc = from_device<T>(ctx, ey + off, dey + off, cnt); if (rc) return rc;
+        rc = from_device<T>(ctx, rho + off, drho + off, cnt); if (rc) return rc;
+        rc = from_device<T>(ctx, theta + off, dth + off, cnt); if (rc) return rc;
     }
-    if (!devp) {
-        int herr = 0;
-        rc = from_device<int64_t>(ctx, count, dcount, (size_t)nb); if (rc) return rc;
-        rc = from_device<double>(ctx, rms, drms, (size_t)nb); if (rc) return rc;
-        if (ft_err) { rc = from_device<int>(ctx, &herr, ft_err, 1); if (rc) return rc; }
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (herr)
-            return fail(ORT_EHIP, "full_trace in-launch hand-off fault (%s): the survivors' offsets are not trustworthy, nothing was returned",
-                        (herr & 2) ? "tile tickets outside the launch: the context's ticket base and the device counter disagree"
-                                   : "a workgroup waited for its predecessors beyond the poll cap");
-        for (int b = 0; b < nb; ++b) {
-            const size_t off = (size_t)b * 2 * rpb, cnt = (size_t)count[b];
-            if (!cnt) continue;
-            rc = from_device<T>(ctx, ex + off, dex + off, cnt); if (rc) return rc;
-            rc = from_device<T>(ctx, ey + off, dey + off, cnt); if (rc) return rc;
-            rc = from_device<T>(ctx, rho + off, drho + off, cnt); if (rc) return rc;
-            rc = from_device<T>(ctx, theta + off, dth + off, cnt); if (rc) return rc;
-        }
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ORT_OK;
 }
 
@@ -674,12 +710,9 @@ int full_trace_impl(ort_ctx* ctx, const ort_system* sys, int nb, const ort_bundl
     if (rpb > 0x7fffffffLL - kTile) return fail(ORT_EINVAL, "bundle of %lld rays is too large (max 2^31)", (long long)rpb);
     const bool devp = flags & ORT_DEVICE_PTRS;
 
-    TraceParams<T> p;
-    memset(&p, 0, sizeof p);
-    p.recs = Sel<T>::rec(sys); p.polys = Sel<T>::poly(sys); p.arms = Sel<T>::arms(sys); p.S = S; p.apert2 = Sel<T>::ap2(sys);
-    rc = upload_bundles<T>(ctx, sys, nb, bundles, ny, nx, axes_len, flags, &p.bundles); if (rc) return rc;
-    p.ny = ny; p.nx = nx; p.rpb = rpb; p.tiles_per_bundle = (int)((rpb + kTile - 1) / kTile);
-    p.raybasis = (flags & ORT_RAYBASIS) ? 1 : 0;
+    TraceParams<T> p = system_params<T>(sys);
+    rc = upload_bundles<T>(ctx, sys, nb, bundles, ny, nx, axes_len, &p.bundles); if (rc) return rc;
+    set_grid_shape(p, ny, nx, flags);
     if (devp) p.axes = axes;
     else { rc = to_device<T>(ctx, SL_AXES, axes, (size_t)axes_len, &p.axes); if (rc) return rc; }
     rc = make_rb_slopes<T>(ctx, p, nb); if (rc) return rc;
@@ -988,19 +1021,6 @@ extern "C" int ort_debug_phase_clocks(ort_ctx* ctx, unsigned long long* out32)
     int rc = check_ctx(ctx); if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpyFromSymbol(out32, HIP_SYMBOL(ort::g_phase), 32 * sizeof(unsigned long long)));
-    return ORT_OK;
-}
-#endif
-
-#ifdef ORT_COUNT_RETRACE
-// measurement build only: {tile-waves traced by MATH_FAST kernels, tile-waves that traced again with the reference sequence} since
-// the last reset (scripts/run_workload.py --retrace)
-extern "C" int ort_debug_retrace_counts(ort_ctx* ctx, unsigned long long* out2, int reset)
-{
-    int rc = check_ctx(ctx); if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpyFromSymbol(out2, HIP_SYMBOL(ort::g_retrace), 2 * sizeof(unsigned long long)));
-    if (reset) { const unsigned long long z[2] = {0, 0}; HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ort::g_retrace), z, sizeof z)); }
     return ORT_OK;
 }
 #endif

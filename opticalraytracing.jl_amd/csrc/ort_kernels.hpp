@@ -29,41 +29,13 @@ __device__ unsigned long long g_phase[32];
 #else
 #define ORT_PHASE(i) do { } while (0)
 #endif
-#ifdef ORT_COUNT_RETRACE             // measurement build only (scripts/run_workload.py --retrace): [0] = tile-waves traced by a
-__device__ unsigned long long g_retrace[2];   // MATH_FAST kernel, [1] = those that traced again with the reference sequence
-#endif
 
-
-// Tunables (compile-time; the defaults are the measured best).
-#ifndef ORT_POLY_WAVES
-#define ORT_POLY_WAVES (ORT_MIN_WAVES - 1)   // waves per SIMD the polynomial-arm builds are compiled for
-#endif
-#ifndef ORT_RPT
-#define ORT_RPT 2            // rays per lane
-#endif
-#ifndef ORT_NT_STORES
-#define ORT_NT_STORES 1      // non-temporal history stores
-#endif
-#ifndef ORT_APERTURES
-#define ORT_APERTURES 1   // 0 compiles the clear-aperture extension out (A/B builds)
-#endif
-#ifndef ORT_FT_DEBUG
-#define ORT_FT_DEBUG 0
-#endif
-#ifndef ORT_MIN_WAVES
-#define ORT_MIN_WAVES 5      // __launch_bounds__ 2nd argument (waves per SIMD): 96 VGPRs, no spill in the fast history kernel
-#endif
-#ifndef ORT_WAVES_NOHIST
-#define ORT_WAVES_NOHIST ORT_MIN_WAVES   // the same for the kernels without history stores (A/B: 6 = 80 VGPRs spills)
-#endif
-#ifndef ORT_WAVES_F32
-#define ORT_WAVES_F32 ORT_WAVES_NOHIST   // the same for the Float32 kernels without history stores
-#endif
-#ifndef ORT_BLOCK
-#define ORT_BLOCK 256          // threads per workgroup (A/B builds: 128 halves the tile and the end-of-launch tail)
-#endif
-constexpr int kBlock = ORT_BLOCK;
-constexpr int kRPT = ORT_RPT;
+// Tunables (the measured best).
+constexpr int kMinWaves = 5;       // __launch_bounds__ 2nd argument (waves per SIMD): 96 VGPRs, no spill in the fast history kernel; the same for
+                                   // the kernels without history stores, the Float32 ones among them (6 = 80 VGPRs spills)
+constexpr int kPolyWaves = kMinWaves - 1;   // waves per SIMD the polynomial-arm builds are compiled for
+constexpr int kBlock = 256;        // threads per workgroup (128 halves the tile and the end-of-launch tail)
+constexpr int kRPT = 2;            // rays per lane
 constexpr int kTile = kBlock * kRPT;
 constexpr int kMaxRows = 64;
 constexpr int kMaxCoef = 12;
@@ -137,19 +109,10 @@ __device__ __forceinline__ void store_pair(T* base, int64_t g, bool two, T a, T 
     const bool aligned = (reinterpret_cast<uintptr_t>(base + g) & (2 * sizeof(T) - 1)) == 0;
     if (two && aligned) {
         typename Vec2<T>::type v2; v2.x = a; v2.y = b;
-#if ORT_NT_STORES
         __builtin_nontemporal_store(v2, reinterpret_cast<typename Vec2<T>::type*>(base + g));
-#else
-        *reinterpret_cast<typename Vec2<T>::type*>(base + g) = v2;
-#endif
     } else {
-#if ORT_NT_STORES
         __builtin_nontemporal_store(a, base + g);
         if (two) __builtin_nontemporal_store(b, base + g + 1);
-#else
-        base[g] = a;
-        if (two) base[g + 1] = b;
-#endif
     }
 }
 
@@ -158,11 +121,7 @@ template <typename T>
 __device__ __forceinline__ void store_vec2(T* p, T a, T b)
 {
     typename Vec2<T>::type v2; v2.x = a; v2.y = b;
-#if ORT_NT_STORES
     __builtin_nontemporal_store(v2, reinterpret_cast<typename Vec2<T>::type*>(p));
-#else
-    *reinterpret_cast<typename Vec2<T>::type*>(p) = v2;
-#endif
 }
 
 // ------------------------------------------------------------------------------------
@@ -604,20 +563,17 @@ __device__ __forceinline__ void ft_place_body(int bid, const T* __restrict__ w_e
 //                BASELINE config 5 (profiles/r04_ab_walk_tiles_per_workgroup.log).
 enum { FT_NONE = 0, FT_FULL = 1, FT_WALK1 = 2, FT_LOOKBACK = 3, FT_WALK = 4, FT_FUSED = 5 };   // FT_WALK1: FT_WALK with spans of ONE tile (compile-time: the
                                                                                // span test of the long-span kernel stays a constant)
-#ifndef ORT_STATUS_ON_DEMAND
-#define ORT_STATUS_ON_DEMAND 1   // summary kernels count the per-surface status only when the caller passed a status array (A/B: 0)
-#endif
-#ifndef ORT_STOP_EXIT
-#define ORT_STOP_EXIT 1       // full_trace kernels: a wave whose rays are all outside the stop ends its surface loop there (A/B: 0 = none, 3 = every kernel)
-#endif
-#ifndef ORT_WALK_TILES
-#define ORT_WALK_TILES 8     // tiles per span of the FT_WALK route for bundles of more than kSmallTiles tiles (a power of two)
-#endif
-constexpr int kWalkTiles = ORT_WALK_TILES;
-#ifndef ORT_SUMM_WALK_F64
-#define ORT_SUMM_WALK_F64 0   // A/B build: the Float64 summary kernels walk tiles as the Float32 ones do
-#endif
-template <typename T> constexpr bool kSummaryWalks = sizeof(T) == 4 || ORT_SUMM_WALK_F64;
+constexpr int kWalkTiles = 8;     // tiles per span of the FT_WALK route for bundles of more than kSmallTiles tiles (a power of two)
+template <typename T> constexpr bool kSummaryWalks = sizeof(T) == 4;   // the Float32 summary kernels walk tiles (SWALK below); Float64: measured, no gain
+// __launch_bounds__ 2nd argument of k_trace.  Both outputs, look-back epilogue, Float64 running sums, polynomial arms: 128 VGPRs
+// (at 96 they park tens of values per row in scratch)
+template <typename T, int ARMS, bool HIST, bool SUMM, int FT>
+constexpr int trace_min_waves()
+{
+    if (ARMS >= ARMS_EVEN) return kPolyWaves;
+    if ((HIST && SUMM) || FT == FT_LOOKBACK || ((FT == FT_WALK || FT == FT_WALK1) && sizeof(T) == 8)) return kMinWaves - 1;
+    return kMinWaves;
+}
 constexpr int kStatusVignetted = 1 << 17, kStatusVigShift = 20;
 // ------------------------------------------------------------------------------------
 // ARMS: the row classes this build carries (surface_step_n): the batch's highest row decides (ort_system::arms).
@@ -626,8 +582,8 @@ constexpr int kStatusVignetted = 1 << 17, kStatusVigShift = 20;
 // one wave's instruction stream, and RPT = 1 — the same 512-ray tile on 512 threads — halves it.  Same results bit for
 // bit (the tile sums are taken in the RPT = 2 order, tile_sum2 below).
 template <typename T, int MATH, int ARMS, bool GRID, bool HIST, bool SUMM, int FT, int RPT = kRPT>
-__global__ __launch_bounds__(kTile / RPT, ARMS >= ARMS_EVEN ? ORT_POLY_WAVES : ((HIST && SUMM) || FT == 3 /* FT_LOOKBACK */ || ((FT == 4 || FT == 2) /* FT_WALK, FT_WALK1 */ && sizeof(T) == 8)) ? ORT_MIN_WAVES - 1 : HIST ? ORT_MIN_WAVES : sizeof(T) == 4 ? ORT_WAVES_F32 : ORT_WAVES_NOHIST)
-void k_trace(TraceParams<T> p)   // both outputs, look-back epilogue, Float64 running sums, polynomial arms: 128 VGPRs (at 96 they park tens of values per row in scratch)
+__global__ __launch_bounds__(kTile / RPT, (trace_min_waves<T, ARMS, HIST, SUMM, FT>()))   // (the macro splits at unparenthesised commas)
+void k_trace(TraceParams<T> p)
 {
     constexpr int NT = kTile / RPT;                              // threads per workgroup: one tile of kTile rays
     constexpr int kSumWaves = kBlock / 64;                       // waves of the RPT = 2 shape: the order the tile sums are taken in
@@ -659,11 +615,7 @@ void k_trace(TraceParams<T> p)   // both outputs, look-back epilogue, Float64 ru
     if (FUSED && tid == 0) s_arrive = 0;                         // (read after the table's barrier at the earliest)
     if (FT == FT_LOOKBACK) {
         if (tid == 0) {
-#if ORT_FT_DEBUG & 2            /* A/B only: blockIdx order instead of tickets (no progress guarantee) */
-            unsigned long long tk = blockIdx.x;
-#else
             unsigned long long tk = atomicAdd(p.ft_ticket, 1ull) - p.ft_ticket_base;
-#endif
             if (tk >= gridDim.x) {                                   // host bookkeeping fault: never index out of the grid, and say so —
                 tk = gridDim.x - 1;                                  // the call returns an error instead of misplaced survivors
                 atomicOr(p.ft_err, 2);
@@ -728,7 +680,7 @@ void k_trace(TraceParams<T> p)   // both outputs, look-back epilogue, Float64 ru
     const T* __restrict__ gpoly = (POLY && p.polys) ? p.polys + (int64_t)sysid * S * kPolyRec : nullptr;
     // clear-aperture extension (no reference counterpart): wave-uniform row pointer, null = off
     typedef const __attribute__((address_space(4))) T* CApPtr;  // wave-uniform address: scalar loads
-    const CApPtr gap2 = (ORT_APERTURES && (SUMM || FT) && p.apert2) ? (CApPtr)(uintptr_t)(p.apert2 + (int64_t)sysid * S) : (CApPtr)0;
+    const CApPtr gap2 = ((SUMM || FT) && p.apert2) ? (CApPtr)(uintptr_t)(p.apert2 + (int64_t)sysid * S) : (CApPtr)0;
 
     bool pf_ok = false;
     int pf_c = 0; int64_t pf_off = 0, pf_m = 0; double pf_mux = 0.0, pf_muy = 0.0, pf_rmax = 0.0;
@@ -870,7 +822,7 @@ void k_trace(TraceParams<T> p)   // both outputs, look-back epilogue, Float64 ru
                 const T* cf = (M == MATH) ? (s_poly + i * kPolyLds) : (gpoly ? gpoly + i * kPolyRec : nullptr);
                 surface_step_n<T, M, RPT, ARMS>(ray, rec, cf, cls, i == S - 1, odd);
                 if (SUMM || FT) {
-                    if (SUMM && (!ORT_STATUS_ON_DEMAND || want_status)) {  // the full_trace epilogue reads the final NaN-ness only: no count;
+                    if (SUMM && want_status) {  // the full_trace epilogue reads the final NaN-ness only: no count;
                                                                          // nor does a summary call that asks for hits without status (scalar branch)
 #pragma unroll
                         for (int r = 0; r < RPT; ++r) {
@@ -888,10 +840,8 @@ void k_trace(TraceParams<T> p)   // both outputs, look-back epilogue, Float64 ru
                         // As a `break` the exit changes how the compiler lays the loop out (Float32: 2,056 -> 1,541 instructions, yet
                         // ort_spot_batch_f32 8.15 -> 9.18 ms); as a bound it still costs the Float32 kernels 4 % (config 5's waves are
                         // whole pupil rows, never all outside) and the plain-sphere Float64 compaction kernel 3 %, so it is taken by
-                        // the Float64 statistics kernels and the polynomial builds only (profiles/r04_ab_stop_exit.log;
-                        // -DORT_STOP_EXIT=3: every full_trace kernel, =0: none)
-                        constexpr bool kStopExit = ORT_STOP_EXIT && FT != FT_NONE && !SUMM && !HIST &&
-                                                   (ORT_STOP_EXIT == 3 || (sizeof(T) == 8 && (WALK || POLY)));      // (which kernels: see below)
+                        // the Float64 statistics kernels and the polynomial builds only (profiles/r04_ab_stop_exit.log)
+                        constexpr bool kStopExit = FT != FT_NONE && !SUMM && !HIST && sizeof(T) == 8 && (WALK || POLY);
                         bool out_all = kStopExit && a_stop >= T(0);
 #pragma unroll
                         for (int r = 0; r < RPT; ++r) {
@@ -931,9 +881,6 @@ void k_trace(TraceParams<T> p)   // both outputs, look-back epilogue, Float64 ru
             return odd;
         };
         const bool odd_seen = trace_surfaces(std::integral_constant<int, MATH>{});
-#ifdef ORT_COUNT_RETRACE
-        if (MATH == MATH_FAST && (tid & 63) == 0) { atomicAdd(&g_retrace[0], 1ull); if (__any(odd_seen)) atomicAdd(&g_retrace[1], 1ull); }
-#endif
         if (MATH == MATH_FAST && __builtin_expect(__any(odd_seen), 0)) {
             // A ray of this wave went where the reference's formulas are no longer the geometry the fast forms compute
             // (a far-cap hit, a direction refracted backward, a polynomial row outside its conic: possible only far
@@ -1132,11 +1079,7 @@ void k_trace(TraceParams<T> p)   // both outputs, look-back epilogue, Float64 ru
                                            __HIP_MEMORY_SCOPE_AGENT);
                     }
                     long long excl = 0;
-#if ORT_FT_DEBUG & 1            /* A/B only: no look-back, every tile writes at its dense position (wrong offsets, same traffic) */
-                    int hi = -1; excl = (long long)tile * kTile * 3 / 4;
-#else
                     int hi = tile - 1;                               // next predecessor to look at
-#endif
                     constexpr int kLook = 4;                         // predecessors per lane and round: windows of 256 tiles
                     while (hi >= 0) {
                         // lane l looks at tiles hi - kLook l - j, j = 0 .. kLook-1 (nearest first); every tile with a lower
@@ -1388,10 +1331,7 @@ __global__ __launch_bounds__(kBlock) void k_ft_stats_reduce_wave(const int32_t* 
 }
 
 // kPlaceTiles consecutive tiles of one bundle per workgroup, their headers fetched together (one round trip for the group).
-#ifndef ORT_PLACE_TILES
-#define ORT_PLACE_TILES 2
-#endif
-constexpr int kPlaceTiles = ORT_PLACE_TILES;
+constexpr int kPlaceTiles = 2;
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_ft_place(const T* __restrict__ w_ex, const T* __restrict__ w_ey,

@@ -5,7 +5,7 @@ thing interleaved A/B timings call.  Prints one JSON line.
   python scripts/run_workload.py config3 --mode stats|full|lookback|fused [--policy fast|ieee] [--pupil 2048] [--reps 5]
   python scripts/run_workload.py config2 --mode summary|history|stats|full
   python scripts/run_workload.py config1 --mode full|stats [--field 1.0]      (one-call pipeline, host buffers)
-  python scripts/run_workload.py config5 --mode stats|hits [--dtype f32|f64] [--instances 10000] [--retrace]
+  python scripts/run_workload.py config5 --mode stats|hits [--dtype f32|f64] [--instances 10000]
         stats: ort_spot_batch_f32 (one C call, host arrays in, 16 B per (instance, field) out: the statistics kernel);
         hits:  the same number of rays through the Float32 summary kernel (image-plane hits, 8 B per ray out)
 """
@@ -25,7 +25,6 @@ def main():
     ap.add_argument("workload", choices=["config1", "config2", "config3", "config4", "config5"])
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"], help="config5: arithmetic of the pupil trace")
     ap.add_argument("--instances", type=int, default=10000, help="config5: perturbed instances")
-    ap.add_argument("--retrace", action="store_true", help="print the retrace counters of an -DORT_COUNT_RETRACE build")
     ap.add_argument("--mode", default="stats")
     ap.add_argument("--policy", default="fast", choices=["fast", "ieee"])
     ap.add_argument("--pupil", type=int, default=0)
@@ -103,11 +102,6 @@ def main():
             fn = lambda: (plan.trace(hits), eng.ctx.synchronize())
             rays = plan.n_rays
         fn(); eng.ctx.synchronize()
-        if a.retrace:
-            cnt = (C.c_ulonglong * 2)()
-            lib.ort_debug_retrace_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-            lib.ort_debug_retrace_counts.restype = C.c_int
-            _capi.check(lib.ort_debug_retrace_counts(h, cnt, 1))
         ts = []
         for _ in range(a.reps):
             t0 = time.perf_counter(); r = fn(); eng.ctx.synchronize(); ts.append(time.perf_counter() - t0)
@@ -115,9 +109,6 @@ def main():
                    wall_ms_min=float(np.min(ts)) * 1e3, intersections_per_s=rays * 12 / float(np.median(ts)))
         if a.mode == "stats":
             res.update(mean_rms=float(np.nanmean(r["rms"])), count_mean=float(r["count"].mean()))
-        if a.retrace:
-            _capi.check(lib.ort_debug_retrace_counts(h, cnt, 0))
-            res.update(tile_waves=int(cnt[0]), tile_waves_retraced=int(cnt[1]), retrace_fraction=cnt[1] / max(1, cnt[0]))
         print(json.dumps(res), flush=True)
         return
 
