@@ -248,6 +248,29 @@ int ort_full_trace_f32(ort_ctx *ctx, const ort_system *sys, int nb, const ort_bu
  * Out of place, like the reference's map; every pointer host or device per ORT_DEVICE_PTRS. */
 int ort_wavegrad_f64(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count, const double *nu, double lambda,
                      const double *ex, const double *ey, double *gx, double *gy, unsigned flags);
+/* Zernike wavefront fit of nb full_trace results, the workflow of the reference's misc/Zernike_fit.jl (wavegrad, then a fit
+ * of Zernike gradients to it) without bringing the vectors to the host.
+ *  - terms: radial degree 1 .. degree (1 <= degree <= 10), piston excluded, OSA/ANSI order: term j = (n (n + 2) + m) / 2 - 1
+ *    for n = 1 .. degree, m = -n, -n + 2, .., n;  nterms = degree (degree + 3) / 2 <= 65.
+ *  - polynomials (Zernike.jl's orthonormal convention): Z_n^m = N_n^m R_n^|m|(rho) cos(m theta) for m >= 0,
+ *    N_n^m R_n^|m|(rho) sin(|m| theta) for m < 0, N_n^m = sqrt(2 (n + 1) / (1 + delta_m0)).
+ *  - pupil coordinates x = rho cos(theta), y = rho sin(theta), rho and theta exactly as full_trace wrote them (mirrored half
+ *    included; rho is already r / maximum(r)).
+ *  - data, per valid entry i < count[b]: gx = ex nu[b] / lambda, gy = ey nu[b] / lambda (wavegrad, fused in: no
+ *    intermediate array is written).
+ *  - coef[b][0 .. nterms) minimises sum_i (sum_j c_j dZ_j/dx(rho_i, theta_i) - gx_i)^2 + (sum_j c_j dZ_j/dy - gy_i)^2, by
+ *    the normal equations (Float64 matrix instructions) and a Cholesky factorisation; the same call gives the same bits.
+ *    resid[b] = RMS of that residual over the 2 count[b] equations, in waves, from a second pass over the rays (the normal
+ *    matrix holds it only to eps x |g|^2).  info[b] = 0: success; info[b] != 0: no fit, coef[b][:] and resid[b] are NaN —
+ *    count[b] <= 0 (an empty bundle, or the -1 of a faulted look-back / fused full_trace) or 2 count[b] < nterms (-1), or
+ *    Cholesky pivot k not positive (k + 1).  The call itself still returns ORT_OK then.
+ * ex, ey, rho, theta : [nb][cap] (cap = the slab stride of ort_full_trace_f64); count, nu : [nb]; coef : [nb][nterms];
+ * resid, info : [nb] or NULL.  Every pointer host or device per ORT_DEVICE_PTRS, as for ort_wavegrad_f64.
+ * ORT_EINVAL: degree outside 1..10, a NULL among the required pointers, lambda <= 0. */
+int ort_zernike_fit_f64(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count, const double *nu, double lambda,
+                        const double *ex, const double *ey, const double *rho, const double *theta,
+                        int degree, double *coef /* [nb][nterms] */, double *resid /* [nb] or NULL */,
+                        int32_t *info /* [nb] or NULL */, unsigned flags);
 /* Testing aid: shift the context's look-back ticket base against the device counter, the bookkeeping fault that
  * ort_full_trace_* with ORT_FT_LOOKBACK must report (ORT_EHIP; device-pointer callers see count = -1, rms = NaN). */
 int ort_ctx_test_skew_tickets(ort_ctx *ctx, int64_t delta);

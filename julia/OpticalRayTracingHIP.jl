@@ -124,6 +124,25 @@ function full_trace_rms(surfaces::Layout, system::System, H::Float64, k_rays::In
     return cnt[], rms[]
 end
 
+"""
+    zernike_fit(ε::RealRayError, degree, λ = 587.5618e-6) -> (c, resid, info)
+
+The workflow of misc/Zernike_fit.jl on the GPU (`ort_zernike_fit_f64`): least-squares coefficients of the orthonormal Zernike
+polynomials of radial degree 1 .. degree (OSA/ANSI order, piston excluded) whose gradients fit `wavegrad(ε, λ)` at (ε.r, ε.t);
+`resid` is the residual RMS in waves, `info == 0` a successful fit.  Device-resident slabs of many bundles take the same call
+with `DeviceArray` pointers and ORT_DEVICE_PTRS.
+"""
+function zernike_fit(ε, degree::Integer, λ::Float64 = 587.5618e-6)
+    n = length(ε.x); nterms = div(degree * (degree + 3), 2)
+    cnt = Int64[n]; nu = Float64[ε.nu]; x = collect(Float64, ε.x); y = collect(Float64, ε.y); r = collect(Float64, ε.r); t = collect(Float64, ε.t)
+    c = Vector{Float64}(undef, nterms); resid = Float64[NaN]; info = Int32[0]
+    GC.@preserve cnt nu x y r t c resid info check(ccall((:ort_zernike_fit_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, UInt32),
+        ctx().h, 1, n, cnt, nu, λ, x, y, r, t, degree, c, resid, info, 0))
+    return c, resid[1], info[1]
+end
+
 "Power-series coefficients of a row's polynomial; the closure handed to the CPU path is built from the same vector."
 poly(c::Vector{Float64}) = OpticalRayTracing.Polynomial(y -> evalpoly(y, c))
 

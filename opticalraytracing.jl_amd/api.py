@@ -854,6 +854,22 @@ def wavegrad(err: RealRayError, lam: float = LAMBDA):                 # PupilSam
     return err.x * err.nu / lam, err.y * err.nu / lam
 
 
+def zernike_terms(degree: int) -> List[Tuple[int, int]]:
+    """(n, m) of the fitted Zernike terms in coefficient order: radial degree 1..degree, piston excluded, OSA/ANSI
+    (j = (n (n + 2) + m) / 2 - 1)."""
+    return [(n, m) for n in range(1, int(degree) + 1) for m in range(-n, n + 1, 2)]
+
+
+def zernike_fit(err: RealRayError, degree: int, lam: float = LAMBDA, engine=None):
+    """Zernike coefficients of the wavefront behind a full_trace result — the reference's misc/Zernike_fit.jl workflow
+    (wavegrad, then a least-squares fit of the orthonormal Zernike gradients at (ε.r, ε.t)) on the GPU (`ort_zernike_fit_f64`).
+    Returns (coefficients in `zernike_terms(degree)` order, residual RMS in waves, info: 0 = fitted).  Device-resident slabs of
+    many bundles: HipEngine.zernike_fit."""
+    coef, resid, info = _eng(engine).zernike_fit(np.atleast_2d(err.x), np.atleast_2d(err.y), np.atleast_2d(err.r), np.atleast_2d(err.t),
+                                                [len(err.x)], [err.nu], lam, degree)
+    return coef[0], float(resid[0]), int(info[0])
+
+
 # ---------------------------------------------------------------------------------------
 # transfer matrix (TransferMatrix.jl)
 # ---------------------------------------------------------------------------------------

@@ -81,7 +81,8 @@ enum { SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, S
        SL_BUNDLES, SL_AXES, SL_WEX, SL_WEY, SL_WR, SL_WTH, SL_TCNT, SL_TSX, SL_TSY, SL_TRM,
        SL_TOFF, SL_TSQ, SL_AGG, SL_RES0, SL_RES1, SL_TAB0, SL_TAB1, SL_TAB2, SL_TAB3,
        SL_SB_FO, SL_SB_REC, SL_SB_MF, SL_SB_MR, SL_SB_TLF, SL_SB_TLR, SL_SB_AIN, SL_SB_AOUT, SL_SB_ENDS, SL_SB_FLAG,
-       SL_SB_FIELDS, SL_SB_A, SL_SB_HP, SL_SB_PACK, SL_SB_CEXT, SL_SB_CREV, SL_FTSTATE, SL_FTTICKET, SL_FTERR, SL_FTDONE, SL_FTREADY, SL_DOMAIN, SL_RBSLOPES, SL_COUNT };
+       SL_SB_FIELDS, SL_SB_A, SL_SB_HP, SL_SB_PACK, SL_SB_CEXT, SL_SB_CREV, SL_FTSTATE, SL_FTTICKET, SL_FTERR, SL_FTDONE, SL_FTREADY, SL_DOMAIN, SL_RBSLOPES,
+       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_COUNT };
 
 }  // namespace
 
@@ -887,6 +888,82 @@ int spot_batch_impl(ort_ctx* ctx, int nsys, int rows, const double* R, const dou
     return ORT_OK;
 }
 
+// ---- Zernike wavefront fit (k_zfit_*, ort_kernels.hpp): how a call is cut into workgroups, its scratch, its launches ----
+constexpr size_t kZfWorkspaceBytes = (size_t)64 << 20;    // cap of the partial-tile workspace: more bundles than fit run in passes
+
+struct ZfitPlan {
+    int nterms;
+    int NT;                  // 16-column blocks of the augmented matrix [G | b]: ceil((nterms + 1) / 16)
+    int ntiles;              // NT (NT + 1) / 2 upper-triangle 16 x 16 tiles
+    int spans;               // workgroups per bundle
+    int parts;               // partial Gram matrices per bundle (spans x the k-split of the one-tile case)
+    int64_t span_rays;       // rays per span, a multiple of the slab
+    int bundles_per_pass;    // bundles whose partial tiles fit the workspace
+};
+
+ZfitPlan zfit_plan(int nb, int64_t cap, int degree, int cus)
+{
+    ZfitPlan pl;
+    pl.nterms = degree * (degree + 3) / 2;
+    pl.NT = (pl.nterms + 1 + 15) / 16;
+    pl.ntiles = pl.NT * (pl.NT + 1) / 2;
+    // Few bundles still fill the GPU — about four workgroups per compute unit — and many bundles take one workgroup each.
+    const int64_t target = 4 * (int64_t)std::max(cus, 1), max_spans = (cap + kZfMinSpanRays - 1) / kZfMinSpanRays;
+    const int64_t spans = std::min(std::max<int64_t>((target + nb - 1) / nb, 1), max_spans);
+    pl.span_rays = ((cap + spans - 1) / spans + kZfRays - 1) / kZfRays * kZfRays;
+    pl.spans = (int)((cap + pl.span_rays - 1) / pl.span_rays);
+    pl.parts = pl.spans * zf_ksplit(pl.NT);
+    const size_t per_bundle = (size_t)pl.parts * pl.ntiles * 256 * sizeof(double);
+    pl.bundles_per_pass = (int)std::min<size_t>(std::max<size_t>(kZfWorkspaceBytes / per_bundle, 1), (size_t)nb);
+    return pl;
+}
+
+template <int NT>
+void zfit_pass(hipStream_t st, const ZfitPlan& pl, const ZfArgs& a, int nbb, double* ws, double* part, double* coef, double* resid,
+               int32_t* info)
+{
+    const dim3 grid((unsigned)nbb * (unsigned)pl.spans), block(kZfBlock);
+    hipLaunchKernelGGL((k_zfit_accumulate<NT>), grid, block, 0, st, a, ws);
+    if (pl.parts > 1)
+        hipLaunchKernelGGL(k_zfit_fold, dim3((unsigned)nbb * (unsigned)pl.ntiles), block, 0, st, pl.parts, pl.ntiles, ws);
+    hipLaunchKernelGGL(k_zfit_solve, dim3((unsigned)nbb), block, 0, st, a.b0, pl.parts, NT, pl.nterms, a.cap, a.count,
+                       (const double*)ws, coef, resid, info);
+    if (resid) {
+        hipLaunchKernelGGL((k_zfit_residual<NT>), grid, block, 0, st, a, (const double*)coef, part);
+        hipLaunchKernelGGL(k_zfit_resid_final, dim3((unsigned)((nbb + kZfBlock - 1) / kZfBlock)), block, 0, st, a.b0, nbb, pl.spans,
+                           a.cap, a.count, (const double*)part, resid);
+    }
+}
+
+// every pointer is a device pointer; resid, info may be null
+int zernike_fit_device(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const double* nu, double lambda,
+                       const double* ex, const double* ey, const double* rho, const double* theta, int degree,
+                       double* coef, double* resid, int32_t* info)
+{
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const ZfitPlan pl = zfit_plan(nb, cap, degree, cus);
+    double *ws = nullptr, *part = nullptr;
+    int rc = dev_out<double>(ctx, SL_ZF_WS, (size_t)pl.bundles_per_pass * pl.parts * pl.ntiles * 256, &ws); if (rc) return rc;
+    rc = dev_out<double>(ctx, SL_ZF_PART, (size_t)pl.bundles_per_pass * pl.spans, &part); if (rc) return rc;
+    ZfArgs a;
+    a.spans = pl.spans; a.degree = degree; a.nterms = pl.nterms; a.span_rays = pl.span_rays; a.cap = cap;
+    a.count = count; a.nu = nu; a.lambda = lambda; a.ex = ex; a.ey = ey; a.rho = rho; a.theta = theta;
+    for (int b0 = 0; b0 < nb; b0 += pl.bundles_per_pass) {       // passes share the workspace: stream order keeps them apart
+        const int nbb = std::min(nb - b0, pl.bundles_per_pass);
+        a.b0 = b0;
+        switch (pl.NT) {
+        case 1: zfit_pass<1>(ctx->stream, pl, a, nbb, ws, part, coef, resid, info); break;
+        case 2: zfit_pass<2>(ctx->stream, pl, a, nbb, ws, part, coef, resid, info); break;
+        case 3: zfit_pass<3>(ctx->stream, pl, a, nbb, ws, part, coef, resid, info); break;
+        case 4: zfit_pass<4>(ctx->stream, pl, a, nbb, ws, part, coef, resid, info); break;
+        default: zfit_pass<5>(ctx->stream, pl, a, nbb, ws, part, coef, resid, info); break;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return ORT_OK;
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -1068,6 +1145,35 @@ int ort_wavegrad_f64(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, co
         rc = from_device<double>(ctx, gy, dgy, n); if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
+    return ORT_OK;
+}
+
+int ort_zernike_fit_f64(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const double* nu, double lambda,
+                        const double* ex, const double* ey, const double* rho, const double* theta,
+                        int degree, double* coef, double* resid, int32_t* info, unsigned flags)
+{
+    int rc = check_ctx(ctx); if (rc) return rc;
+    if (nb <= 0 || cap <= 0 || !count || !nu || !ex || !ey || !rho || !theta || !coef || !(lambda > 0.0))
+        return fail(ORT_EINVAL, "bad zernike_fit arguments");
+    if (degree < 1 || degree > kZfMaxDegree) return fail(ORT_EINVAL, "zernike_fit: degree %d outside 1..%d", degree, kZfMaxDegree);
+    if ((flags & ORT_DEVICE_PTRS))
+        return zernike_fit_device(ctx, nb, cap, count, nu, lambda, ex, ey, rho, theta, degree, coef, resid, info);
+    const size_t n = (size_t)nb * (size_t)cap, nterms = (size_t)(degree * (degree + 3) / 2);
+    const int64_t* dcount; const double *dnu, *dex, *dey, *drho, *dth; double *dcoef, *dresid = nullptr; int32_t* dinfo = nullptr;
+    rc = to_device<int64_t>(ctx, SL_IN0, count, (size_t)nb, &dcount); if (rc) return rc;
+    rc = to_device<double>(ctx, SL_IN1, nu, (size_t)nb, &dnu); if (rc) return rc;
+    rc = to_device<double>(ctx, SL_IN2, ex, n, &dex); if (rc) return rc;
+    rc = to_device<double>(ctx, SL_IN3, ey, n, &dey); if (rc) return rc;
+    rc = to_device<double>(ctx, SL_ZF_RHO, rho, n, &drho); if (rc) return rc;
+    rc = to_device<double>(ctx, SL_ZF_THETA, theta, n, &dth); if (rc) return rc;
+    rc = dev_out<double>(ctx, SL_OUT0, (size_t)nb * nterms, &dcoef); if (rc) return rc;
+    if (resid) { rc = dev_out<double>(ctx, SL_OUT1, (size_t)nb, &dresid); if (rc) return rc; }
+    if (info) { rc = dev_out<int32_t>(ctx, SL_OUT2, (size_t)nb, &dinfo); if (rc) return rc; }
+    rc = zernike_fit_device(ctx, nb, cap, dcount, dnu, lambda, dex, dey, drho, dth, degree, dcoef, dresid, dinfo); if (rc) return rc;
+    rc = from_device<double>(ctx, coef, dcoef, (size_t)nb * nterms); if (rc) return rc;      // nterms + 2 numbers per bundle come back
+    if (resid) { rc = from_device<double>(ctx, resid, dresid, (size_t)nb); if (rc) return rc; }
+    if (info) { rc = from_device<int32_t>(ctx, info, dinfo, (size_t)nb); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ORT_OK;
 }
 

@@ -2523,4 +2523,361 @@ __global__ __launch_bounds__(kBlock) void k_abcd_transfer(const double* __restri
     }
 }
 
+
+// ------------------------------------------------------------------------------------
+// Zernike wavefront fit of full_trace results on the device (ort_zernike_fit_f64, include/ort.h).
+//
+// Least squares of the transverse errors in waves (wavegrad, src/PupilSampling.jl:165-167) against the Cartesian gradients
+// of the orthonormal Zernike polynomials: min_c |G c - b|^2 with two rows per ray (d/dx, d/dy).  Float64 throughout.
+//
+//   k_zfit_accumulate<NT>   the augmented Gram matrix [G | b]^T [G | b] of a span of one bundle's rays, by
+//                           v_mfma_f64_16x16x4_f64 on gradient rows built in LDS; one set of upper-triangle tiles per
+//                           workgroup, stored plainly to a workspace slot (no floating-point atomics)
+//   k_zfit_fold             a bundle's partial tiles summed in span order (bit-reproducible)
+//   k_zfit_solve            Cholesky of the normal matrix with the right-hand side riding as one more row, back substitution
+//   k_zfit_residual<NT>     |G c - b|^2 of a span, from the same rows: the residual is NOT taken from the Gram matrix
+//   k_zfit_resid_final      RMS over the 2 count equations
+//
+// Gradient rows.  With z = x + i y = rho e^{i theta}, t = 2 rho^2 - 1, s = (n - mu) / 2:
+//     R_n^mu(rho) cos(mu theta) = P_s^{(0,mu)}(t) Re z^mu,        R_n^mu(rho) sin(mu theta) = P_s^{(0,mu)}(t) Im z^mu
+// (P: Jacobi polynomials), so
+//     d/dx = 4 x P' Re z^mu + mu P Re z^(mu-1),                    d/dy = 4 y P' Re z^mu - mu P Im z^(mu-1)      (cos terms)
+//     d/dx = 4 x P' Im z^mu + mu P Im z^(mu-1),                    d/dy = 4 y P' Im z^mu + mu P Re z^(mu-1)      (sin terms)
+// P and P' come from the three-term recurrence in s (that is, in n at fixed mu), z^mu from repeated complex multiplication
+// by z — the angle-addition recurrence on one sincos(theta), carrying rho^mu along.  R_n^mu / rho never appears: nothing
+// divides by rho and a ray at rho = 0 is exact.
+// ------------------------------------------------------------------------------------
+// All of it is Float64; the packed-FP32 instruction forms are switched off for these functions (device pass only: the host
+// compiler does not know the feature), so that no helper arithmetic added later is paired into them unnoticed.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define ORT_ZF_FN __attribute__((target("no-packed-fp32-ops")))
+#else
+#define ORT_ZF_FN
+#endif
+
+constexpr int kZfMaxDegree = 10;              // nterms = degree (degree + 3) / 2 <= 65
+constexpr int kZfBlock = 256;                 // 4 waves
+constexpr int kZfRays = 32;                   // rays per slab
+constexpr int kZfRows = 2 * kZfRays;          // gradient rows per slab
+constexpr int kZfKSteps = kZfRows / 4;        // MFMA k-steps per slab
+constexpr int kZfMinSpanRays = 8 * kZfRays;   // a workgroup's set-up and its stored tiles are worth at least this many rays
+constexpr int kZfMaxM = kZfMaxDegree * (kZfMaxDegree + 3) / 2 + 1;   // 66: terms + right-hand side
+
+typedef double zf_d4 __attribute__((ext_vector_type(4)));
+
+// Row stride of the LDS tile in doubles: 16 NT, padded to an odd number of 16-double blocks so that the four rows of a
+// k-step — read by the four 16-lane groups of a wave, 128 contiguous bytes each — alternate between the two halves of the banks.
+ORT_ZF_FN constexpr int zf_ld(int NT) { return 16 * (NT | 1); }
+// One tile (NT = 1) leaves three waves without a tile: there the four waves split the k-steps and store four partial tiles.
+ORT_ZF_FN constexpr int zf_ksplit(int NT) { return NT == 1 ? 4 : 1; }
+// Tile p of the upper triangle, row by row: (0,0) (0,1) ... (0,NT-1) (1,1) ...
+ORT_ZF_FN constexpr int zf_tile_row(int NT, int p) { int I = 0; while (p >= NT - I) { p -= NT - I; ++I; } return I; }
+ORT_ZF_FN constexpr int zf_tile_col(int NT, int p) { int I = 0; while (p >= NT - I) { p -= NT - I; ++I; } return I + p; }
+ORT_ZF_FN constexpr int zf_tile_index(int NT, int I, int J) { return I * NT - I * (I - 1) / 2 + (J - I); }
+// Element (i, j) of a tile as v_mfma_f64_16x16x4_f64 leaves it: register i / 4 of lane 16 (i % 4) + j; stored register-major.
+ORT_ZF_FN constexpr int zf_tile_offset(int i, int j) { return (i >> 2) * 64 + (i & 3) * 16 + j; }
+
+// Coefficients of P_s = (A t + B) P_{s-1} - C P_{s-2} for P_s^{(0,mu)}, s >= 2, and the normalisation N_n^m.
+struct ZfTab {
+    double A[kZfMaxDegree / 2 + 1][kZfMaxDegree + 1], B[kZfMaxDegree / 2 + 1][kZfMaxDegree + 1], C[kZfMaxDegree / 2 + 1][kZfMaxDegree + 1];
+    double N0[kZfMaxDegree + 1], N1[kZfMaxDegree + 1];      // sqrt(n + 1) (m = 0), sqrt(2 (n + 1)) (m != 0)
+};
+constexpr int kZfTabEntries = (kZfMaxDegree / 2 + 1) * (kZfMaxDegree + 1);
+
+ORT_ZF_FN __device__ __forceinline__ void zf_tab_entry(ZfTab& T, int e)
+{
+    const int s = e / (kZfMaxDegree + 1), mu = e % (kZfMaxDegree + 1);
+    double A = 0.0, B = 0.0, C = 0.0;
+    if (s >= 2) {
+        const double c = 2.0 * s + mu, d = (double)s * (s + mu);
+        A = (c - 1.0) * c / (2.0 * d);
+        B = -(c - 1.0) * (double)(mu * mu) / (2.0 * d * (c - 2.0));
+        C = (double)(s - 1) * (s + mu - 1) * c / (d * (c - 2.0));
+    }
+    T.A[s][mu] = A; T.B[s][mu] = B; T.C[s][mu] = C;
+    if (e <= kZfMaxDegree) { T.N0[e] = sqrt((double)(e + 1)); T.N1[e] = sqrt(2.0 * (e + 1)); }
+}
+
+// All terms of angular order mu up to `degree` at one point: rowx[j] = dZ_j/dx, rowy[j] = dZ_j/dy for m = +mu and (mu > 0)
+// m = -mu, j in OSA/ANSI order without piston.  (zr, zi) = z^mu, (wr, wi) = z^(mu-1) (anything finite for mu = 0); scale multiplies
+// every value (0 for a padding ray).
+ORT_ZF_FN __device__ __forceinline__ void zf_chain(const ZfTab& T, int mu, int degree, double x, double y, double zr, double zi,
+                                         double wr, double wi, double scale, double* rowx, double* rowy)
+{
+    const double t = 2.0 * (x * x + y * y) - 1.0, fm = (double)mu;
+    double Pp = 0.0, Dp = 0.0, P = 1.0, D = 0.0;                 // P_{s-1}, P'_{s-1}, P_s, P'_s
+    for (int s = 0, n = mu; n <= degree; ++s, n += 2) {
+        if (s == 1) {
+            Pp = P; Dp = D;
+            P = 0.5 * ((fm + 2.0) * t - fm); D = 0.5 * (fm + 2.0);
+        } else if (s >= 2) {
+            const double A = T.A[s][mu], a = A * t + T.B[s][mu], c = T.C[s][mu];
+            const double Pn = a * P - c * Pp, Dn = A * P + a * D - c * Dp;
+            Pp = P; Dp = D; P = Pn; D = Dn;
+        }
+        if (n == 0) continue;                                    // piston
+        const double N = (mu == 0 ? T.N0[n] : T.N1[n]) * scale;
+        const double jp = 4.0 * D, jm = fm * P;
+        const int j = (n * (n + 2) + mu) / 2 - 1;
+        rowx[j] = N * (jp * x * zr + jm * wr); rowy[j] = N * (jp * y * zr - jm * wi);
+        if (mu > 0) { rowx[j - mu] = N * (jp * x * zi + jm * wi); rowy[j - mu] = N * (jp * y * zi + jm * wr); }
+    }
+}
+
+struct ZfArgs {
+    int b0, spans, degree, nterms;
+    int64_t span_rays, cap;
+    const int64_t* count;
+    const double* nu;
+    double lambda;
+    const double *ex, *ey, *rho, *theta;
+};
+
+struct ZfShared {
+    ZfTab tab;
+    double x[kZfRays], y[kZfRays], scale[kZfRays];
+};
+
+// The span of bundle b this workgroup walks: rays [lo, hi) of its slab; empty for a bundle without valid entries
+// (count <= 0: the empty bundle, or the -1 of a faulted look-back / fused full_trace).
+ORT_ZF_FN __device__ __forceinline__ void zf_span(const ZfArgs& a, int b, int span, int64_t* lo, int64_t* hi)
+{
+    int64_t n = a.count[b];
+    n = n < a.cap ? n : a.cap;
+    *lo = (int64_t)span * a.span_rays;
+    const int64_t end = *lo + a.span_rays;
+    *hi = end < n ? end : n;
+}
+
+ORT_ZF_FN __device__ __forceinline__ void zf_prepare(double* Gs, int ld, ZfShared& sh, int tid)
+{
+    for (int i = tid; i < kZfRows * ld; i += kZfBlock) Gs[i] = 0.0;          // padding columns stay zero for the whole walk
+    if (tid < kZfTabEntries) zf_tab_entry(sh.tab, tid);
+}
+
+// One slab: the gradient rows of rays [base, base + 32) of bundle b into Gs[64][LD], the right-hand side in column nterms.
+// Rays at or past hi are zero rows.  All 256 threads: 8 per ray, thread `sub` of a ray takes the angular orders sub, sub + 8.
+template <int NT>
+ORT_ZF_FN __device__ __forceinline__ void zf_fill_slab(double* Gs, ZfShared& sh, const ZfArgs& a, int b, int tid, int64_t base, int64_t hi)
+{
+    constexpr int LD = zf_ld(NT);
+    __syncthreads();                                             // the previous slab's readers are done
+    if (tid < kZfRays) {
+        const int64_t i = base + tid;
+        const bool ok = i < hi;
+        double x = 0.0, y = 0.0, gx = 0.0, gy = 0.0;
+        if (ok) {
+            const int64_t o = (int64_t)b * a.cap + i;
+            const double nub = a.nu[b];
+            double sn, cs;
+            sincos(a.theta[o], &sn, &cs);
+            const double r = a.rho[o];
+            x = r * cs; y = r * sn;
+            gx = (a.ex[o] * nub) / a.lambda;                     // wavegrad, fused in
+            gy = (a.ey[o] * nub) / a.lambda;
+        }
+        sh.x[tid] = x; sh.y[tid] = y; sh.scale[tid] = ok ? 1.0 : 0.0;
+        Gs[(2 * tid) * LD + a.nterms] = gx;
+        Gs[(2 * tid + 1) * LD + a.nterms] = gy;
+    }
+    __syncthreads();
+    const int ray = tid >> 3, sub = tid & 7;
+    const double x = sh.x[ray], y = sh.y[ray], scale = sh.scale[ray];
+    double* rowx = Gs + (2 * ray) * LD;
+    double* rowy = rowx + LD;
+    double zr = 1.0, zi = 0.0, wr = 0.0, wi = 0.0;
+    int k = 0;
+    for (int mu = sub; mu <= a.degree; mu += 8) {
+        for (; k < mu; ++k) {                                    // z^k -> z^(k+1)
+            wr = zr; wi = zi;
+            const double nr = zr * x - zi * y;
+            zi = zr * y + zi * x; zr = nr;
+        }
+        zf_chain(sh.tab, mu, a.degree, x, y, zr, zi, wr, wi, scale, rowx, rowy);
+    }
+    __syncthreads();
+}
+
+// The MFMA phase of wave W over one slab.  For a k-step of 4 rows lane l holds g_t = Gs[4 ks + l / 16][16 t + l % 16] for
+// every column block t; that one register is the A operand (a 16 x 4 slice of G^T) of every tile of block row t and the B
+// operand (4 x 16 slice of G) of every tile of block column t: C_IJ += g_I^T g_J.  No transposed copy exists.
+template <int NT, int W>
+ORT_ZF_FN __device__ __forceinline__ void zf_mma(const double* Gs, int lane, zf_d4 (&acc)[4])
+{
+    constexpr int LD = zf_ld(NT), NTP = NT * (NT + 1) / 2, KS = zf_ksplit(NT);
+    const double* row0 = Gs + (lane >> 4) * LD + (lane & 15);
+    for (int ks = (KS > 1 ? W : 0); ks < kZfKSteps; ks += KS) {
+        const double* row = row0 + 4 * ks * LD;
+        double g[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) g[t] = row[16 * t];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int p = KS > 1 ? (q == 0 ? 0 : NTP) : W + 4 * q;
+            if (p < NTP)
+                acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(g[zf_tile_row(NT, p)], g[zf_tile_col(NT, p)], acc[q], 0, 0, 0);
+        }
+    }
+}
+
+template <int NT, int W>
+ORT_ZF_FN __device__ __forceinline__ void zf_store(const zf_d4 (&acc)[4], double* slot /* this span's first part */, int lane)
+{
+    constexpr int NTP = NT * (NT + 1) / 2, KS = zf_ksplit(NT);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int p = KS > 1 ? (q == 0 ? 0 : NTP) : W + 4 * q;
+        if (p < NTP) {
+            double* dst = slot + (size_t)(KS > 1 ? W * NTP : p) * 256;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) dst[v * 64 + lane] = acc[q][v];
+        }
+    }
+}
+
+// Grid: bundles x spans.  ws : [bundle][parts = spans x ksplit][NTP][256].
+template <int NT>
+__global__ ORT_ZF_FN __launch_bounds__(kZfBlock) void k_zfit_accumulate(ZfArgs a, double* __restrict__ ws)
+{
+    constexpr int LD = zf_ld(NT), NTP = NT * (NT + 1) / 2, KS = zf_ksplit(NT);
+    __shared__ double Gs[kZfRows * LD];
+    __shared__ ZfShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bl = blockIdx.x / a.spans, span = blockIdx.x - bl * a.spans, b = a.b0 + bl;
+    int64_t lo, hi;
+    zf_span(a, b, span, &lo, &hi);
+    zf_prepare(Gs, LD, sh, tid);
+    zf_d4 acc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] = zf_d4{0.0, 0.0, 0.0, 0.0};
+    for (int64_t base = lo; base < hi; base += kZfRays) {
+        zf_fill_slab<NT>(Gs, sh, a, b, tid, base, hi);
+        if (wave == 0) zf_mma<NT, 0>(Gs, lane, acc);
+        else if (wave == 1) zf_mma<NT, 1>(Gs, lane, acc);
+        else if (wave == 2) zf_mma<NT, 2>(Gs, lane, acc);
+        else zf_mma<NT, 3>(Gs, lane, acc);
+    }
+    double* slot = ws + ((size_t)bl * a.spans + span) * KS * NTP * 256;
+    if (wave == 0) zf_store<NT, 0>(acc, slot, lane);
+    else if (wave == 1) zf_store<NT, 1>(acc, slot, lane);
+    else if (wave == 2) zf_store<NT, 2>(acc, slot, lane);
+    else zf_store<NT, 3>(acc, slot, lane);
+}
+
+// A bundle's parts summed in part order into its part 0.  Grid: bundles x NTP, one thread per tile element.
+__global__ ORT_ZF_FN __launch_bounds__(kZfBlock) void k_zfit_fold(int parts, int ntiles, double* __restrict__ ws)
+{
+    const int bl = blockIdx.x / ntiles, p = blockIdx.x - bl * ntiles;
+    double* e = ws + ((size_t)bl * parts * ntiles + p) * 256 + threadIdx.x;
+    const size_t stride = (size_t)ntiles * 256;
+    double s = e[0];
+    for (int q = 1; q < parts; ++q) s += e[q * stride];
+    e[0] = s;
+}
+
+// One workgroup per bundle: the upper-triangle tiles mirrored into LDS, then a right-looking Cholesky of the nterms x nterms
+// block in the lower triangle with the right-hand side as row nterms (which so becomes y = L^-1 G^T b), then L^T c = y.
+// info: 0, -1 (count <= 0 or fewer equations than terms), k + 1 (pivot k not positive); on info != 0 c and resid are NaN.
+__global__ ORT_ZF_FN __launch_bounds__(kZfBlock) void k_zfit_solve(int b0, int parts, int NT, int nterms, int64_t cap,
+                                                         const int64_t* __restrict__ count, const double* __restrict__ ws,
+                                                         double* __restrict__ coef, double* __restrict__ resid,
+                                                         int32_t* __restrict__ info)
+{
+    __shared__ double A[kZfMaxM][kZfMaxM + 1];
+    __shared__ double sd[kZfMaxM], cs[kZfMaxM];
+    const int tid = threadIdx.x, bl = blockIdx.x, b = b0 + bl;
+    const int M = nterms + 1, ntiles = NT * (NT + 1) / 2;
+    int64_t n = count[b];
+    n = n < cap ? n : cap;
+    const double* wb = ws + (size_t)bl * parts * ntiles * 256;
+    for (int e = tid; e < M * M; e += kZfBlock) {
+        const int r = e / M, c = e - r * M;
+        if (r > c) continue;
+        const double s = wb[zf_tile_index(NT, r >> 4, c >> 4) * 256 + zf_tile_offset(r & 15, c & 15)];
+        A[r][c] = s; A[c][r] = s;
+    }
+    __syncthreads();
+    int fail = (n <= 0 || 2 * n < nterms) ? -1 : 0;
+    for (int k = 0; k < nterms && !fail; ++k) {
+        const double d = A[k][k];                                // the same value in every thread: the exit is uniform
+        if (!(d > 0.0)) { fail = k + 1; break; }
+        const double s = sqrt(d);
+        if (tid == 0) sd[k] = s;
+        if (tid > k && tid < M) A[tid][k] = A[tid][k] / s;       // column k of L, the right-hand side's row included
+        __syncthreads();
+        const int w = M - k - 1;
+        for (int e = tid; e < w * w; e += kZfBlock) {
+            const int i = k + 1 + e / w, j = k + 1 + e % w;
+            if (j <= i && j < nterms) A[i][j] -= A[i][k] * A[j][k];
+        }
+        __syncthreads();
+    }
+    if (!fail)
+        for (int k = nterms - 1; k >= 0; --k) {
+            const double ck = A[nterms][k] / sd[k];
+            if (tid == 0) cs[k] = ck;
+            if (tid < k) A[nterms][tid] -= A[k][tid] * ck;
+            __syncthreads();
+        }
+    const double nan = __builtin_nan("");
+    if (tid < nterms) coef[(size_t)b * nterms + tid] = fail ? nan : cs[tid];
+    if (tid == 0) {
+        if (resid) resid[b] = fail ? nan : 0.0;                  // k_zfit_resid_final fills the successful ones in
+        if (info) info[b] = fail;
+    }
+}
+
+// |G c - b|^2 over a span.  The Gram matrix also holds b^T b - c^T G^T b, but only to eps x b^T b: a fit whose residual is
+// 1e-3 of the data would keep three digits of its RMS.  The rows are rebuilt instead (no MFMA: one dot product per row).
+template <int NT>
+__global__ ORT_ZF_FN __launch_bounds__(kZfBlock) void k_zfit_residual(ZfArgs a, const double* __restrict__ coef, double* __restrict__ part)
+{
+    constexpr int LD = zf_ld(NT);
+    __shared__ double Gs[kZfRows * LD];
+    __shared__ ZfShared sh;
+    __shared__ double cs[kZfMaxM];
+    __shared__ double red[kZfBlock];
+    const int tid = threadIdx.x;
+    const int bl = blockIdx.x / a.spans, span = blockIdx.x - bl * a.spans, b = a.b0 + bl;
+    int64_t lo, hi;
+    zf_span(a, b, span, &lo, &hi);
+    if (coef[(size_t)b * a.nterms] != coef[(size_t)b * a.nterms]) hi = lo;      // no fit (NaN row, k_zfit_solve): nothing to walk
+    zf_prepare(Gs, LD, sh, tid);
+    if (tid < a.nterms) cs[tid] = coef[(size_t)b * a.nterms + tid];
+    const int row = tid >> 2, q = tid & 3;
+    double acc = 0.0;
+    for (int64_t base = lo; base < hi; base += kZfRays) {
+        zf_fill_slab<NT>(Gs, sh, a, b, tid, base, hi);
+        const double* g = Gs + row * LD;
+        double s = 0.0;
+        for (int j = q; j < a.nterms; j += 4) s += g[j] * cs[j];
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        const double r = s - g[a.nterms];
+        if (q == 0) acc += r * r;
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int w = kZfBlock / 2; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) part[(size_t)bl * a.spans + span] = red[0];
+}
+
+__global__ ORT_ZF_FN __launch_bounds__(kZfBlock) void k_zfit_resid_final(int b0, int nb, int spans, int64_t cap, const int64_t* __restrict__ count,
+                                                               const double* __restrict__ part, double* __restrict__ resid)
+{
+    const int bl = blockIdx.x * kZfBlock + threadIdx.x;
+    if (bl >= nb) return;
+    const int b = b0 + bl;
+    if (resid[b] != resid[b]) return;                            // no fit (k_zfit_solve)
+    double s = 0.0;
+    for (int q = 0; q < spans; ++q) s += part[(size_t)bl * spans + q];
+    const int64_t n = count[b] < cap ? count[b] : cap;
+    resid[b] = sqrt(s / (2.0 * (double)n));
+}
+
+#undef ORT_ZF_FN
+
 }  // namespace ort

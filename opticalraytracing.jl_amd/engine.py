@@ -206,6 +206,30 @@ class HipEngine:
                                             ptr(gx), ptr(gy), flags))
         return gx, gy
 
+    # ---- Zernike wavefront fit of full_trace results: the workflow of misc/Zernike_fit.jl ----
+    def zernike_fit(self, ex, ey, rho, theta, count, nu, lam: float, degree: int):
+        """`ort_zernike_fit_f64`: least-squares Zernike coefficients (radial degree 1..degree, OSA/ANSI order, piston excluded)
+        of the wavefront whose gradient is wavegrad(ex, ey) at the pupil points (rho, theta), for nb full_trace slabs [nb][cap].
+        Returns (coef [nb][nterms], resid [nb] RMS in waves, info [nb]: 0 = fitted, otherwise the row is NaN).  numpy arrays go
+        through host buffers; torch CUDA tensors (all six inputs) stay on the device — nothing is copied, the call is
+        asynchronous on the engine's stream and the results are torch tensors."""
+        nb, cap = ex.shape
+        nterms = max(int(degree), 0) * (int(degree) + 3) // 2
+        if hasattr(ex, "data_ptr"):
+            import torch
+            coef = torch.empty((nb, nterms), dtype=torch.float64, device=ex.device)
+            resid = torch.empty(nb, dtype=torch.float64, device=ex.device)
+            info = torch.empty(nb, dtype=torch.int32, device=ex.device)
+            flags = self.base_flags | _capi.ORT_DEVICE_PTRS
+        else:
+            ex, ey, rho, theta = f64(ex), f64(ey), f64(rho), f64(theta)
+            count = np.ascontiguousarray(count, dtype=np.int64); nu = np.ascontiguousarray(np.broadcast_to(f64(nu), (nb,)))
+            coef = np.empty((nb, nterms)); resid = np.empty(nb); info = np.empty(nb, dtype=np.int32)
+            flags = self.base_flags
+        check(self.ctx.lib.ort_zernike_fit_f64(self.ctx.h, int(nb), int(cap), ptr(count), ptr(nu), float(lam), ptr(ex), ptr(ey),
+                                               ptr(rho), ptr(theta), int(degree), ptr(coef), ptr(resid), ptr(info), flags))
+        return coef, resid, info
+
     # ---- meridional: raytrace(surfaces, y, U, RealRay)  RayTracing.jl:145-169 -----------
     def meridional(self, pres: Prescription, y, U, layout_mode: bool = False, isys: int = 0):
         y, U = (np.atleast_1d(f64(a)) for a in (y, U))
