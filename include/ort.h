@@ -37,7 +37,8 @@
 extern "C" {
 #endif
 
-#define ORT_VERSION 401            /* 0.4.1: ORT_FT_FUSED (full_trace's second pass inside the trace launch; bit-identical results) and its
+#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64 and ort_psf_f64: new entry points only, nothing existing moved)
+                                      0.4.1: ORT_FT_FUSED (full_trace's second pass inside the trace launch; bit-identical results) and its
                                       testing aid ort_ctx_test_fused_no_scan.  0.4.0: no new entry point; statistics-only full_trace walks tiles per workgroup (results within 1e-12 of
                                       0.3.0's); the device-side aiming loops trace without trigonometric calls only under ORT_FAST_MATH;
                                       the one-call pipelines report look-back faults to host callers; a context may be destroyed ahead of
@@ -271,6 +272,29 @@ int ort_zernike_fit_f64(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count,
                         const double *ex, const double *ey, const double *rho, const double *theta,
                         int degree, double *coef /* [nb][nterms] */, double *resid /* [nb] or NULL */,
                         int32_t *info /* [nb] or NULL */, unsigned flags);
+/* Diffraction point-spread function and Strehl ratio of nb Zernike wavefronts, what the coefficients of ort_zernike_fit_f64 do
+ * to the image, without bringing them to the host (no reference counterpart: the reference stops at the fit).
+ *  - coef, degree, term order and normalisation: exactly those of ort_zernike_fit_f64, in waves;
+ *    W(x, y) = sum_j c_j Z_j(rho, theta), x = rho cos(theta), y = rho sin(theta), on the whole unit disc.
+ *  - pupil: the midpoint grid x_k = (2 k + 1 - npupil) / npupil, k = 0 .. npupil - 1, the same for y; a node belongs to the
+ *    pupil when x_k^2 + y_j^2 <= 1; N = number of such nodes.
+ *  - image samples: xi_m = xi_c + (m - nimg / 2) dxi, eta the same, in the units of wavegrad (an image displacement eps is
+ *    xi = eps nu / lambda); centre[b] = {xi_c, eta_c}.
+ *  - psf[b][my][mx] = | sum_{(j,k) in pupil} exp(i 2 pi (W(x_k, y_j) - xi_mx x_k - eta_my y_j)) |^2 / N^2: an unaberrated
+ *    pupil gives exactly 1 at xi = eta = 0.  Float64 matrix instructions form the double sum as E P E^T.
+ *  - strehl[b] = the value at sample (nimg / 2, nimg / 2).  That sample is always taken from one plain sum over the pupil in
+ *    a fixed order, in the full call too (where it is written into psf[b] as well): strehl[b] is bit-identical to
+ *    psf[b][nimg / 2][nimg / 2], with or without psf, and from call to call.
+ *  - psf == NULL: only strehl is computed — no matrix product, 8 bytes per bundle leave the device.
+ *  - a bundle with info[b] != 0, or whose coef[b][0] is NaN (no fit), gets NaN in psf[b] and strehl[b]; the call returns ORT_OK.
+ * coef : [nb][nterms]; info : [nb] or NULL; centre : [nb][2] or NULL (zeros); psf : [nb][nimg][nimg] or NULL; strehl : [nb].
+ * Every pointer host or device per ORT_DEVICE_PTRS, as for ort_zernike_fit_f64.
+ * ORT_EINVAL: degree outside 1..10, npupil not a multiple of 16 in 32..1024, nimg not a multiple of 16 in 16..128, dxi <= 0,
+ * NULL coef or strehl. */
+int ort_psf_f64(ort_ctx *ctx, int nb, int degree, const double *coef /* [nb][nterms] */,
+                const int32_t *info /* [nb] or NULL */, int npupil, int nimg, double dxi,
+                const double *centre /* [nb][2] = {xi_c, eta_c}, or NULL = 0 */,
+                double *psf /* [nb][nimg][nimg] or NULL */, double *strehl /* [nb] */, unsigned flags);
 /* Testing aid: shift the context's look-back ticket base against the device counter, the bookkeeping fault that
  * ort_full_trace_* with ORT_FT_LOOKBACK must report (ORT_EHIP; device-pointer callers see count = -1, rms = NaN). */
 int ort_ctx_test_skew_tickets(ort_ctx *ctx, int64_t delta);

@@ -143,6 +143,22 @@ function zernike_fit(ε, degree::Integer, λ::Float64 = 587.5618e-6)
     return c, resid[1], info[1]
 end
 
+"""
+    psf(c, degree; npupil = 128, nimg = 64, dxi = 0.125, centre = (0.0, 0.0)) -> (psf, strehl)
+
+Diffraction point-spread function (`nimg × nimg`, `psf[mx, my]`) and Strehl ratio of the wavefront with the Zernike coefficients
+`c` of `zernike_fit` (`ort_psf_f64`): the image sampled at `centre .+ (m - nimg ÷ 2) * dxi` in `wavegrad` units on an
+`npupil × npupil` midpoint grid of the unit disc; 1 at the peak of an unaberrated pupil.
+"""
+function psf(c::Vector{Float64}, degree::Integer; npupil::Integer = 128, nimg::Integer = 64, dxi::Float64 = 0.125, centre = (0.0, 0.0))
+    length(c) == div(degree * (degree + 3), 2) || throw(DimensionMismatch("degree $degree takes $(div(degree * (degree + 3), 2)) coefficients"))
+    ctr = Float64[centre[1], centre[2]]; out = Matrix{Float64}(undef, nimg, nimg); strehl = Float64[NaN]
+    GC.@preserve c ctr out strehl check(ccall((:ort_psf_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Int32}, Cint, Cint, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32),
+        ctx().h, 1, degree, c, C_NULL, npupil, nimg, dxi, ctr, out, strehl, 0))
+    return out, strehl[1]
+end
+
 "Power-series coefficients of a row's polynomial; the closure handed to the CPU path is built from the same vector."
 poly(c::Vector{Float64}) = OpticalRayTracing.Polynomial(y -> evalpoly(y, c))
 

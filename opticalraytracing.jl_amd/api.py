@@ -870,6 +870,16 @@ def zernike_fit(err: RealRayError, degree: int, lam: float = LAMBDA, engine=None
     return coef[0], float(resid[0]), int(info[0])
 
 
+def psf(coef, degree: int, npupil: int = 128, nimg: int = 64, dxi: float = 0.125, centre=None, engine=None):
+    """Diffraction point-spread function and Strehl ratio of the wavefront with the Zernike coefficients `coef` (one vector in
+    `zernike_terms(degree)` order, waves — the first result of `zernike_fit`) on the GPU (`ort_psf_f64`): (psf [nimg][nimg],
+    strehl), the image sampled at centre + (m - nimg / 2) dxi in wavegrad units, 1 at the peak of an unaberrated pupil.
+    Device-resident coefficients of many bundles, or the Strehl ratio alone: HipEngine.psf."""
+    p, s = _eng(engine).psf(np.atleast_2d(np.asarray(coef, dtype=np.float64)), degree, npupil, nimg, dxi,
+                            centre=None if centre is None else np.atleast_2d(np.asarray(centre, dtype=np.float64)))
+    return p[0], float(s[0])
+
+
 # ---------------------------------------------------------------------------------------
 # transfer matrix (TransferMatrix.jl)
 # ---------------------------------------------------------------------------------------

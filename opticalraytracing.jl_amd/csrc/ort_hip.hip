@@ -82,7 +82,7 @@ enum { SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, S
        SL_TOFF, SL_TSQ, SL_AGG, SL_RES0, SL_RES1, SL_TAB0, SL_TAB1, SL_TAB2, SL_TAB3,
        SL_SB_FO, SL_SB_REC, SL_SB_MF, SL_SB_MR, SL_SB_TLF, SL_SB_TLR, SL_SB_AIN, SL_SB_AOUT, SL_SB_ENDS, SL_SB_FLAG,
        SL_SB_FIELDS, SL_SB_A, SL_SB_HP, SL_SB_PACK, SL_SB_CEXT, SL_SB_CREV, SL_FTSTATE, SL_FTTICKET, SL_FTERR, SL_FTDONE, SL_FTREADY, SL_DOMAIN, SL_RBSLOPES,
-       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_COUNT };
+       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_COUNT };
 
 }  // namespace
 
@@ -964,6 +964,83 @@ int zernike_fit_device(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, 
     return ORT_OK;
 }
 
+// ---- PSF / Strehl ratio of Zernike wavefronts (k_psf_*, ort_kernels.hpp) ----
+struct PsfPlan {
+    int MT;                  // 16-sample tiles per image row
+    int npanels;             // 16-row pupil panels
+    int spans, span_panels;  // workgroups per bundle, panels per workgroup
+    int bundles_per_pass;    // bundles whose partial amplitudes fit the workspace (spans > 1 only)
+    double n2;               // N^2, N = nodes inside the disc
+};
+
+PsfPlan psf_plan(int nb, int npupil, int nimg, int cus)
+{
+    PsfPlan pl;
+    pl.MT = nimg / 16;
+    pl.npanels = npupil / 16;
+    // Few bundles are cut into spans of panels, about four workgroups per compute unit; from that many bundles on, one
+    // workgroup walks a whole bundle, keeps U in registers and writes |U|^2 / N^2 itself: no workspace, one pass.
+    const int64_t target = 4 * (int64_t)std::max(cus, 1);
+    const int64_t spans = std::min<int64_t>(std::max<int64_t>((target + nb - 1) / nb, 1), pl.npanels);
+    pl.span_panels = (int)((pl.npanels + spans - 1) / spans);
+    pl.spans = (pl.npanels + pl.span_panels - 1) / pl.span_panels;
+    const size_t per_bundle = (size_t)pl.spans * 2 * nimg * nimg * sizeof(double);
+    pl.bundles_per_pass = pl.spans == 1 ? nb : (int)std::min<size_t>(std::max<size_t>(kZfWorkspaceBytes / per_bundle, 1), (size_t)nb);
+    int64_t n = 0;
+    for (int j = 0; j < npupil / 2; ++j)                         // one quadrant: the grid is symmetric in both axes
+        for (int k = 0; k < npupil / 2; ++k) n += psf_inside(psf_coord(k, npupil), psf_coord(j, npupil));
+    pl.n2 = (double)(4 * n) * (double)(4 * n);
+    return pl;
+}
+
+template <int MT>
+void psf_launch_accumulate(hipStream_t st, unsigned grid, const PsfArgs& a)
+{
+    if constexpr (MT <= kPsfMaxMT) {
+        if (a.nimg == 16 * MT) hipLaunchKernelGGL((k_psf_accumulate<MT>), dim3(grid), dim3(kPsfBlock), 0, st, a);
+        else psf_launch_accumulate<MT + 1>(st, grid, a);
+    }
+}
+
+// every pointer is a device pointer; info, centre, psf may be null
+int psf_device(ort_ctx* ctx, int nb, int degree, const double* coef, const int32_t* info, int npupil, int nimg, double dxi,
+               const double* centre, double* psf, double* strehl)
+{
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const PsfPlan pl = psf_plan(nb, npupil, nimg, cus);
+    const size_t plane = (size_t)nimg * nimg;
+    PsfArgs a;
+    a.spans = pl.spans; a.span_panels = pl.span_panels; a.degree = degree; a.nterms = degree * (degree + 3) / 2;
+    a.npupil = npupil; a.nimg = nimg; a.n2 = pl.n2; a.coef = coef; a.info = info; a.centre = centre;
+    a.ws = nullptr; a.psum = nullptr; a.psf = psf; a.strehl = strehl; a.b0 = 0;
+    a.tw = nullptr;
+    if (!psf) {                                                  // Strehl only: no table, no matrix product
+        hipLaunchKernelGGL(k_psf_strehl, dim3((unsigned)nb), dim3(kPsfBlock), 0, ctx->stream, a);
+        HIP_TRY(hipGetLastError());
+        return ORT_OK;
+    }
+    double* tw = nullptr;
+    int rc = dev_out<double>(ctx, SL_PSF_TW, (size_t)2 * npupil * nimg, &tw); if (rc) return rc;
+    a.tw = tw;
+    if (pl.spans > 1) {
+        rc = dev_out<double>(ctx, SL_PSF_WS, (size_t)pl.bundles_per_pass * pl.spans * 2 * plane, &a.ws); if (rc) return rc;
+        rc = dev_out<double>(ctx, SL_PSF_SUM, (size_t)pl.bundles_per_pass * pl.npanels * 2, &a.psum); if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_psf_twiddle, dim3((unsigned)((npupil * nimg + kPsfBlock - 1) / kPsfBlock)), dim3(kPsfBlock), 0, ctx->stream,
+                       npupil, nimg, dxi, tw);
+    for (int b0 = 0; b0 < nb; b0 += pl.bundles_per_pass) {       // passes share the workspace: stream order keeps them apart
+        const int nbb = std::min(nb - b0, pl.bundles_per_pass);
+        a.b0 = b0;
+        psf_launch_accumulate<1>(ctx->stream, (unsigned)nbb * (unsigned)pl.spans, a);
+        if (pl.spans > 1)
+            hipLaunchKernelGGL(k_psf_fold, dim3((unsigned)nbb * (unsigned)((plane + kPsfBlock - 1) / kPsfBlock)), dim3(kPsfBlock), 0,
+                               ctx->stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return ORT_OK;
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -1173,6 +1250,29 @@ int ort_zernike_fit_f64(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count,
     rc = from_device<double>(ctx, coef, dcoef, (size_t)nb * nterms); if (rc) return rc;      // nterms + 2 numbers per bundle come back
     if (resid) { rc = from_device<double>(ctx, resid, dresid, (size_t)nb); if (rc) return rc; }
     if (info) { rc = from_device<int32_t>(ctx, info, dinfo, (size_t)nb); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ORT_OK;
+}
+
+int ort_psf_f64(ort_ctx* ctx, int nb, int degree, const double* coef, const int32_t* info, int npupil, int nimg, double dxi,
+                const double* centre, double* psf, double* strehl, unsigned flags)
+{
+    int rc = check_ctx(ctx); if (rc) return rc;
+    if (nb <= 0 || !coef || !strehl || !(dxi > 0.0)) return fail(ORT_EINVAL, "bad psf arguments");
+    if (degree < 1 || degree > kZfMaxDegree) return fail(ORT_EINVAL, "psf: degree %d outside 1..%d", degree, kZfMaxDegree);
+    if (npupil < 32 || npupil > 1024 || npupil % 16) return fail(ORT_EINVAL, "psf: npupil %d is not a multiple of 16 in 32..1024", npupil);
+    if (nimg < 16 || nimg > 16 * kPsfMaxMT || nimg % 16) return fail(ORT_EINVAL, "psf: nimg %d is not a multiple of 16 in 16..%d", nimg, 16 * kPsfMaxMT);
+    if ((flags & ORT_DEVICE_PTRS)) return psf_device(ctx, nb, degree, coef, info, npupil, nimg, dxi, centre, psf, strehl);
+    const size_t nterms = (size_t)(degree * (degree + 3) / 2), plane = (size_t)nimg * nimg;
+    const double *dcoef, *dcentre = nullptr; const int32_t* dinfo = nullptr; double *dpsf = nullptr, *dstrehl;
+    rc = to_device<double>(ctx, SL_IN0, coef, (size_t)nb * nterms, &dcoef); if (rc) return rc;
+    if (info) { rc = to_device<int32_t>(ctx, SL_IN1, info, (size_t)nb, &dinfo); if (rc) return rc; }
+    if (centre) { rc = to_device<double>(ctx, SL_IN2, centre, (size_t)nb * 2, &dcentre); if (rc) return rc; }
+    if (psf) { rc = dev_out<double>(ctx, SL_OUT0, (size_t)nb * plane, &dpsf); if (rc) return rc; }
+    rc = dev_out<double>(ctx, SL_OUT1, (size_t)nb, &dstrehl); if (rc) return rc;
+    rc = psf_device(ctx, nb, degree, dcoef, dinfo, npupil, nimg, dxi, dcentre, dpsf, dstrehl); if (rc) return rc;
+    if (psf) { rc = from_device<double>(ctx, psf, dpsf, (size_t)nb * plane); if (rc) return rc; }
+    rc = from_device<double>(ctx, strehl, dstrehl, (size_t)nb); if (rc) return rc;      // Strehl only: 8 bytes per bundle come back
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ORT_OK;
 }

@@ -2878,6 +2878,272 @@ __global__ ORT_ZF_FN __launch_bounds__(kZfBlock) void k_zfit_resid_final(int b0,
     resid[b] = sqrt(s / (2.0 * (double)n));
 }
 
+
+// ------------------------------------------------------------------------------------
+// Diffraction PSF and Strehl ratio of Zernike wavefronts on the device (ort_psf_f64, include/ort.h).
+//
+// W = sum_j c_j Z_j on the midpoint grid of the unit disc (npupil x npupil nodes, N of them inside), and
+//     psf[my][mx] = | sum_{(j,k) in pupil} exp(i 2 pi (W(x_k, y_j) - xi_mx x_k - eta_my y_j)) |^2 / N^2
+// as the complex matrix triple product U = E P E^T with
+//     P[j][k] = mask exp(i 2 pi (W - xi_c x_k - eta_c y_j))      (the bundle's centre folded into the pupil field)
+//     E[m][k] = exp(-i 2 pi (m - nimg / 2) dxi x_k)              (one table per call: the x and the y grid are the same)
+//
+//   k_psf_twiddle           E, stored pupil-index-major: tw[part][k][m] (part 0 = real, 1 = imaginary), so that the 16 image
+//                           samples a 16-lane group of an MFMA operand holds are contiguous in BOTH stages
+//   k_psf_accumulate<MT>    MT = nimg / 16.  A workgroup walks a span of 16-row pupil panels of one bundle.  Stage 1, per
+//                           16 x 16 chunk of the panel: one node per thread builds P into LDS (column-major: an A operand is 64
+//                           contiguous doubles), then T[16][nimg] += P E^T by v_mfma_f64_16x16x4_f64 — the complex product as
+//                           four real MFMAs.  Wave w owns the image column tiles w, w + 4, .. of T and of U.  Stage 2, per
+//                           panel: U += E_panel^T T.  Register v of a lane's T tile is row 4 v + lane / 16 of the panel —
+//                           exactly the B operand of k-step v — so T goes from the accumulators straight back into the
+//                           matrix pipe: no LDS round trip, no barrier, U (MT ceil(MT / 4) complex tiles: 128 registers at
+//                           nimg = 128) never leaves the registers.  Chunks wholly outside the disc are skipped.
+//                           One span per bundle: |U|^2 / N^2 is written at once; several: U goes plainly to a workspace slot.
+//   k_psf_fold              a bundle's slots summed in span order, |U|^2 / N^2
+//   k_psf_strehl            psf == NULL: the plain sum alone, one workgroup per bundle
+//
+// The centre sample.  E is exactly 1 there, so the amplitude is the plain sum of P.  Every route takes it from that sum, not
+// from the matrix pipe: per panel the nodes are summed per thread in chunk order, over the workgroup in a fixed tree
+// (psf_reduce), and the panels are added in panel order — whichever workgroup walked them.  strehl[b] and the centre sample
+// of psf[b] are therefore the same bits in the full call, in the Strehl-only call and under every split into spans.
+// ------------------------------------------------------------------------------------
+constexpr int kPsfBlock = 256;                // 4 waves; one node of a 16 x 16 chunk per thread
+constexpr int kPsfMaxMT = 8;                  // nimg <= 128: the accumulator tiles of U fill the register file there
+
+// Pupil coordinate k of the midpoint grid, and the mask, in the one form host and device share.
+ORT_ZF_FN __host__ __device__ inline double psf_coord(int k, int npupil) { return (double)(2 * k + 1 - npupil) / (double)npupil; }
+ORT_ZF_FN __host__ __device__ inline bool psf_inside(double x, double y) { return x * x + y * y <= 1.0; }
+// The index of [k0, k0 + 16) nearest the grid's centre: a chunk is outside the disc iff its node at (nearest row, nearest column) is.
+ORT_ZF_FN __host__ __device__ inline int psf_nearest(int k0, int npupil)
+{
+    const int half = npupil / 2;
+    return k0 + 15 < half ? k0 + 15 : (k0 > half ? k0 : half);
+}
+ORT_ZF_FN __device__ __forceinline__ double psf_intensity(double re, double im, double n2) { return (re * re + im * im) / n2; }
+
+struct PsfArgs {
+    int b0, spans, span_panels, degree, nterms, npupil, nimg;
+    double n2;                                // N^2
+    const double* coef;                       // [nb][nterms]
+    const int32_t* info;                      // [nb] or null
+    const double* centre;                     // [nb][2] or null
+    const double* tw;                         // [2][npupil][nimg]
+    double* ws;                               // [bundle of the pass][span][2][nimg][nimg]
+    double* psum;                             // [bundle of the pass][panel][2]
+    double *psf, *strehl;
+};
+
+struct PsfShared {
+    ZfTab tab;
+    double cs[kZfMaxM];
+    double xc, yc;
+    double red[8];
+};
+
+__global__ ORT_ZF_FN __launch_bounds__(kPsfBlock) void k_psf_twiddle(int npupil, int nimg, double dxi, double* __restrict__ tw)
+{
+    const int e = blockIdx.x * kPsfBlock + threadIdx.x;
+    if (e >= npupil * nimg) return;
+    const int k = e / nimg, m = e - k * nimg;
+    double s, c;
+    sincospi(-2.0 * (((double)(m - nimg / 2) * dxi) * psf_coord(k, npupil)), &s, &c);
+    tw[e] = c; tw[(size_t)npupil * nimg + e] = s;
+}
+
+// Coefficients, recurrence table and centre of bundle b into LDS; returns whether the bundle has a wavefront at all.
+ORT_ZF_FN __device__ __forceinline__ bool psf_prepare(PsfShared& sh, const PsfArgs& a, int b, int tid)
+{
+    if (tid < kZfTabEntries) zf_tab_entry(sh.tab, tid);
+    if (tid < a.nterms) sh.cs[tid] = a.coef[(size_t)b * a.nterms + tid];
+    if (tid == 0) { sh.xc = a.centre ? a.centre[2 * (size_t)b] : 0.0; sh.yc = a.centre ? a.centre[2 * (size_t)b + 1] : 0.0; }
+    __syncthreads();
+    return !(a.info && a.info[b] != 0) && sh.cs[0] == sh.cs[0];
+}
+
+// P at one node: the value half of zf_chain's recurrences (P_s^{(0,mu)}(t) by the three-term recurrence, z^mu by repeated
+// multiplication), summed against the coefficients; nothing divides by rho.
+ORT_ZF_FN __device__ __forceinline__ void psf_node(const PsfShared& sh, int degree, double x, double y, double* pr, double* pi)
+{
+    if (!psf_inside(x, y)) { *pr = 0.0; *pi = 0.0; return; }
+    const ZfTab& T = sh.tab;
+    const double t = 2.0 * (x * x + y * y) - 1.0;
+    double W = 0.0, zr = 1.0, zi = 0.0;
+    for (int mu = 0; mu <= degree; ++mu) {
+        if (mu > 0) { const double nr = zr * x - zi * y; zi = zr * y + zi * x; zr = nr; }
+        const double fm = (double)mu;
+        double Pp = 0.0, P = 1.0;
+        for (int s = 0, n = mu; n <= degree; ++s, n += 2) {
+            if (s == 1) { Pp = P; P = 0.5 * ((fm + 2.0) * t - fm); }
+            else if (s >= 2) { const double Pn = (T.A[s][mu] * t + T.B[s][mu]) * P - T.C[s][mu] * Pp; Pp = P; P = Pn; }
+            if (n == 0) continue;                                // piston
+            const int j = (n * (n + 2) + mu) / 2 - 1;
+            double v = sh.cs[j] * zr;
+            if (mu > 0) v += sh.cs[j - mu] * zi;
+            W += ((mu == 0 ? T.N0[n] : T.N1[n]) * P) * v;
+        }
+    }
+    sincospi(2.0 * (W - sh.xc * x - sh.yc * y), pi, pr);
+}
+
+// Sum of (r, i) over the workgroup in a fixed tree: butterfly inside each wave, then the four waves in order.  Every thread
+// returns the same value.
+ORT_ZF_FN __device__ __forceinline__ void psf_reduce(double& r, double& i, double* red, int tid)
+{
+    for (int off = 32; off > 0; off >>= 1) { r += __shfl_xor(r, off); i += __shfl_xor(i, off); }
+    __syncthreads();                                             // the previous panel's readers are done
+    if ((tid & 63) == 0) { red[2 * (tid >> 6)] = r; red[2 * (tid >> 6) + 1] = i; }
+    __syncthreads();
+    r = ((red[0] + red[2]) + red[4]) + red[6];
+    i = ((red[1] + red[3]) + red[5]) + red[7];
+}
+
+// Grid: bundles of the pass x spans.
+template <int MT>
+__global__ ORT_ZF_FN __launch_bounds__(kPsfBlock, MT <= 4 ? 2 : 1) void k_psf_accumulate(PsfArgs a)
+{
+    constexpr int C = (MT + 3) / 4;                              // image column tiles per wave
+    __shared__ PsfShared sh;
+    __shared__ double Pre[256], Pim[256];                        // P^T of the chunk: [column][row]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bl = blockIdx.x / a.spans, span = blockIdx.x - bl * a.spans, b = a.b0 + bl;
+    const int npupil = a.npupil, nimg = a.nimg, npanels = npupil / 16;
+    const bool direct = a.spans == 1;
+    const int p_lo = span * a.span_panels, p_hi = min(p_lo + a.span_panels, npanels);
+    const bool ok = psf_prepare(sh, a, b, tid);
+    const double* twr = a.tw + (lane & 15);
+    const double* twi = twr + (size_t)npupil * nimg;
+    const int g = lane >> 4;                                     // the row of a k-step this lane holds
+    bool on[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) on[c] = (MT % 4 == 0 || c < C - 1) ? true : wave + 4 * c < MT;      // only a last, partial round of tiles can lack a wave
+    zf_d4 Ur[C][MT], Ui[C][MT];
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) { Ur[c][m] = zf_d4{0.0, 0.0, 0.0, 0.0}; Ui[c][m] = zf_d4{0.0, 0.0, 0.0, 0.0}; }
+    double sr = 0.0, si = 0.0;                                   // the plain sum of the panels so far (direct route)
+    for (int p = ok ? p_lo : p_hi; p < p_hi; ++p) {
+        const int j0 = 16 * p;
+        const double yn = psf_coord(psf_nearest(j0, npupil), npupil), y = psf_coord(j0 + (tid & 15), npupil);
+        zf_d4 Tr[C], Ti[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) { Tr[c] = zf_d4{0.0, 0.0, 0.0, 0.0}; Ti[c] = zf_d4{0.0, 0.0, 0.0, 0.0}; }
+        double qr = 0.0, qi = 0.0;
+        for (int k0 = 0; k0 < npupil; k0 += 16) {
+            if (!psf_inside(psf_coord(psf_nearest(k0, npupil), npupil), yn)) continue;      // uniform over the workgroup
+            double pr, pi;
+            psf_node(sh, a.degree, psf_coord(k0 + (tid >> 4), npupil), y, &pr, &pi);
+            qr += pr; qi += pi;
+            __syncthreads();                                     // the previous chunk's readers are done
+            Pre[tid] = pr; Pim[tid] = pi;
+            __syncthreads();
+            // stage 1: T += P E^T.  A[i][k] = P[j0 + i][k0 + 4 ks + k] (lane = 16 k + i), B[k][n] = E[16 mt + n][k0 + 4 ks + k]
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const double ar = Pre[64 * ks + lane], ai = Pim[64 * ks + lane], nai = -ai;
+                const size_t row = (size_t)(k0 + 4 * ks + g) * nimg;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    if (!on[c]) continue;
+                    const int col = 16 * (wave + 4 * c);
+                    const double er = twr[row + col], ei = twi[row + col];
+                    Tr[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, er, Tr[c], 0, 0, 0);
+                    Tr[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(nai, ei, Tr[c], 0, 0, 0);
+                    Ti[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, ei, Ti[c], 0, 0, 0);
+                    Ti[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, er, Ti[c], 0, 0, 0);
+                }
+            }
+        }
+        psf_reduce(qr, qi, sh.red, tid);
+        if (direct) { sr += qr; si += qi; }
+        else if (tid == 0) { double* q = a.psum + 2 * ((size_t)bl * npanels + p); q[0] = qr; q[1] = qi; }
+        // stage 2: U += E_panel^T T.  A[i][k] = E[16 mty + i][j0 + 4 ks + k]; B[k][n] = T[4 ks + k][n] = register ks of the T tile
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const size_t row = (size_t)(j0 + 4 * ks + g) * nimg;
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const double er = twr[row + 16 * m], ei = twi[row + 16 * m], nei = -ei;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    if (!on[c]) continue;
+                    Ur[c][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(er, Tr[c][ks], Ur[c][m], 0, 0, 0);
+                    Ur[c][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(nei, Ti[c][ks], Ur[c][m], 0, 0, 0);
+                    Ui[c][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(er, Ti[c][ks], Ui[c][m], 0, 0, 0);
+                    Ui[c][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(ei, Tr[c][ks], Ui[c][m], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // element (my, mx) = (16 m + 4 v + lane / 16, 16 (wave + 4 c) + lane % 16) is register v of tile [c][m]
+    const double nan = __builtin_nan("");
+    const size_t plane = (size_t)nimg * nimg;
+    const int centre = (nimg / 2) * nimg + nimg / 2;
+    double* slot = a.ws + ((size_t)bl * a.spans + span) * 2 * plane;
+    double* out = a.psf + (size_t)b * plane;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (!on[c]) continue;
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int e = (16 * m + 4 * v + g) * nimg + 16 * (wave + 4 * c) + (lane & 15);
+                if (!direct) { slot[e] = Ur[c][m][v]; slot[plane + e] = Ui[c][m][v]; }
+                else if (e != centre) out[e] = ok ? psf_intensity(Ur[c][m][v], Ui[c][m][v], a.n2) : nan;
+            }
+    }
+    if (direct && tid == 0) {
+        const double s = ok ? psf_intensity(sr, si, a.n2) : nan;
+        out[centre] = s; a.strehl[b] = s;
+    }
+}
+
+// Grid: bundles of the pass x ceil(nimg^2 / 256), one thread per image sample.
+__global__ ORT_ZF_FN __launch_bounds__(kPsfBlock) void k_psf_fold(PsfArgs a)
+{
+    const size_t plane = (size_t)a.nimg * a.nimg;
+    const int per = (int)((plane + kPsfBlock - 1) / kPsfBlock);
+    const int bl = blockIdx.x / per, b = a.b0 + bl, npanels = a.npupil / 16;
+    const int e = (blockIdx.x - bl * per) * kPsfBlock + threadIdx.x;
+    if (e >= (int)plane) return;
+    const bool ok = !(a.info && a.info[b] != 0) && a.coef[(size_t)b * a.nterms] == a.coef[(size_t)b * a.nterms];
+    const bool centre = e == (a.nimg / 2) * a.nimg + a.nimg / 2;
+    double re = 0.0, im = 0.0;
+    if (ok && centre) {
+        const double* q = a.psum + 2 * (size_t)bl * npanels;
+        for (int p = 0; p < npanels; ++p) { re += q[2 * p]; im += q[2 * p + 1]; }
+    } else if (ok) {
+        const double* slot = a.ws + (size_t)bl * a.spans * 2 * plane + e;
+        for (int s = 0; s < a.spans; ++s) { re += slot[(size_t)s * 2 * plane]; im += slot[(size_t)s * 2 * plane + plane]; }
+    }
+    const double val = ok ? psf_intensity(re, im, a.n2) : __builtin_nan("");
+    a.psf[(size_t)b * plane + e] = val;
+    if (centre) a.strehl[b] = val;
+}
+
+// The psf == NULL route.  Grid: bundles.
+__global__ ORT_ZF_FN __launch_bounds__(kPsfBlock) void k_psf_strehl(PsfArgs a)
+{
+    __shared__ PsfShared sh;
+    const int tid = threadIdx.x, b = a.b0 + blockIdx.x, npupil = a.npupil;
+    const bool ok = psf_prepare(sh, a, b, tid);
+    double sr = 0.0, si = 0.0;
+    for (int j0 = ok ? 0 : npupil; j0 < npupil; j0 += 16) {
+        const double yn = psf_coord(psf_nearest(j0, npupil), npupil), y = psf_coord(j0 + (tid & 15), npupil);
+        double qr = 0.0, qi = 0.0;
+        for (int k0 = 0; k0 < npupil; k0 += 16) {
+            if (!psf_inside(psf_coord(psf_nearest(k0, npupil), npupil), yn)) continue;
+            double pr, pi;
+            psf_node(sh, a.degree, psf_coord(k0 + (tid >> 4), npupil), y, &pr, &pi);
+            qr += pr; qi += pi;
+        }
+        psf_reduce(qr, qi, sh.red, tid);
+        sr += qr; si += qi;
+    }
+    if (tid == 0) a.strehl[b] = ok ? psf_intensity(sr, si, a.n2) : __builtin_nan("");
+}
+
 #undef ORT_ZF_FN
 
 }  // namespace ort

@@ -230,6 +230,32 @@ class HipEngine:
                                                ptr(rho), ptr(theta), int(degree), ptr(coef), ptr(resid), ptr(info), flags))
         return coef, resid, info
 
+    # ---- diffraction PSF / Strehl ratio of Zernike wavefronts ----
+    def psf(self, coef, degree: int, npupil: int, nimg: int, dxi: float, centre=None, info=None, want_psf: bool = True):
+        """`ort_psf_f64`: the point-spread function [nb][nimg][nimg] and the Strehl ratio [nb] of the wavefronts whose Zernike
+        coefficients are coef [nb][nterms] (the output of `zernike_fit`, in waves), sampled at xi = centre + (m - nimg / 2) dxi in
+        wavegrad units on an npupil x npupil midpoint grid of the unit disc.  Returns (psf or None, strehl); want_psf = False
+        computes the Strehl ratio alone.  Rows with info != 0 or NaN coefficients give NaN.  numpy arrays go through host
+        buffers; torch CUDA tensors (coef, and centre / info when given) stay on the device — the call is asynchronous on the
+        engine's stream and the results are torch tensors."""
+        nb = coef.shape[0]
+        if hasattr(coef, "data_ptr"):
+            import torch
+            psf = torch.empty((nb, nimg, nimg), dtype=torch.float64, device=coef.device) if want_psf else None
+            strehl = torch.empty(nb, dtype=torch.float64, device=coef.device)
+            flags = self.base_flags | _capi.ORT_DEVICE_PTRS
+        else:
+            coef = f64(coef)
+            centre = None if centre is None else f64(centre)
+            info = None if info is None else np.ascontiguousarray(info, dtype=np.int32)
+            psf = np.empty((nb, nimg, nimg)) if want_psf else None
+            strehl = np.empty(nb)
+            flags = self.base_flags
+        check(self.ctx.lib.ort_psf_f64(self.ctx.h, int(nb), int(degree), ptr(coef), None if info is None else ptr(info), int(npupil),
+                                       int(nimg), float(dxi), None if centre is None else ptr(centre),
+                                       None if psf is None else ptr(psf), ptr(strehl), flags))
+        return psf, strehl
+
     # ---- meridional: raytrace(surfaces, y, U, RealRay)  RayTracing.jl:145-169 -----------
     def meridional(self, pres: Prescription, y, U, layout_mode: bool = False, isys: int = 0):
         y, U = (np.atleast_1d(f64(a)) for a in (y, U))
