@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64 and ort_psf_f64: new entry points only, nothing existing moved)
+#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64 and ort_mtf_f64: new entry points only, nothing existing moved)
                                       0.4.1: ORT_FT_FUSED (full_trace's second pass inside the trace launch; bit-identical results) and its
                                       testing aid ort_ctx_test_fused_no_scan.  0.4.0: no new entry point; statistics-only full_trace walks tiles per workgroup (results within 1e-12 of
                                       0.3.0's); the device-side aiming loops trace without trigonometric calls only under ORT_FAST_MATH;
@@ -295,6 +295,29 @@ int ort_psf_f64(ort_ctx *ctx, int nb, int degree, const double *coef /* [nb][nte
                 const int32_t *info /* [nb] or NULL */, int npupil, int nimg, double dxi,
                 const double *centre /* [nb][2] = {xi_c, eta_c}, or NULL = 0 */,
                 double *psf /* [nb][nimg][nimg] or NULL */, double *strehl /* [nb] */, unsigned flags);
+/* Tangential and sagittal optical transfer function (OTF) and its modulus (MTF) of nb Zernike wavefronts: the exact
+ * autocorrelation of the discretised pupil field, not an FFT of a sampled PSF.
+ *  - coef, degree, term order, normalisation and the pupil: exactly those of ort_psf_f64 — midpoint grid
+ *    x_k = (2 k + 1 - npupil) / npupil, mask x^2 + y^2 <= 1, N nodes inside; P[j][k] = mask exp(i 2 pi W(x_k, y_j)), zero
+ *    outside the grid.
+ *  - axis 0 shears along x: H_0(d) = (1 / N) sum_{j,k} P[j][k + d] conj(P[j][k]);
+ *    axis 1 shears along y: H_1(d) = (1 / N) sum_{j,k} P[j + d][k] conj(P[j][k]);   d = 0 .. npupil - 1.
+ *    otf[b][axis][d] = {Re H, Im H}, mtf[b][axis][d] = |H|.  Negative shears are the complex conjugate and are not stored.
+ *  - sample d lies at 2 d / npupil cycles per unit of xi (the wavegrad units of ort_psf_f64); the cut-off is 2, one sample
+ *    beyond the last stored one.  Multiply by |nu| / lambda for cycles per length unit of the prescription.
+ *  - for a field along y, axis 0 is the sagittal curve and axis 1 the tangential one.
+ *  - sign: a tilt a Z_1^1 = 2 a x gives H_0(d) = |H_0(d)| exp(+i 2 pi 2 a 2 d / npupil), consistent with the PSF peak moving
+ *    to xi = +2 a.  H(0) = 1 to rounding.
+ *  - a bundle with info[b] != 0, or whose coef[b][0] is NaN (no fit), gets NaN in all its outputs; the call returns ORT_OK.
+ *  - the same call gives the same bits from run to run and with host or device pointers; mtf is hypot() of exactly the two
+ *    numbers written to otf (Borges' corrected algorithm in plain IEEE operations, as the GNU C library evaluates it).
+ * coef : [nb][nterms]; info : [nb] or NULL; otf : [nb][2][npupil][2] or NULL; mtf : [nb][2][npupil] or NULL.
+ * Every pointer host or device per ORT_DEVICE_PTRS, as for ort_psf_f64.
+ * ORT_EINVAL: degree outside 1..10, npupil not a multiple of 16 in 32..1024, NULL coef, otf and mtf both NULL. */
+int ort_mtf_f64(ort_ctx *ctx, int nb, int degree, const double *coef /* [nb][nterms] */,
+                const int32_t *info /* [nb] or NULL */, int npupil,
+                double *otf /* [nb][2][npupil][2] or NULL */, double *mtf /* [nb][2][npupil] or NULL */,
+                unsigned flags);
 /* Testing aid: shift the context's look-back ticket base against the device counter, the bookkeeping fault that
  * ort_full_trace_* with ORT_FT_LOOKBACK must report (ORT_EHIP; device-pointer callers see count = -1, rms = NaN). */
 int ort_ctx_test_skew_tickets(ort_ctx *ctx, int64_t delta);

@@ -159,6 +159,22 @@ function psf(c::Vector{Float64}, degree::Integer; npupil::Integer = 128, nimg::I
     return out, strehl[1]
 end
 
+"""
+    mtf(c, degree; npupil = 128) -> (freq, mtf_sagittal, mtf_tangential)
+
+Sagittal and tangential MTF of the wavefront with the Zernike coefficients `c` of `zernike_fit`, for a field along y
+(`ort_mtf_f64`): the modulus of the autocorrelation of the pupil field of `psf` along x and along y, sample `d` at
+`2d / npupil` cycles per `wavegrad` unit (cut-off 2).
+"""
+function mtf(c::Vector{Float64}, degree::Integer; npupil::Integer = 128)
+    length(c) == div(degree * (degree + 3), 2) || throw(DimensionMismatch("degree $degree takes $(div(degree * (degree + 3), 2)) coefficients"))
+    out = Matrix{Float64}(undef, npupil, 2)
+    GC.@preserve c out check(ccall((:ort_mtf_f64, LIB), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Int32}, Cint, Ptr{Float64}, Ptr{Float64}, UInt32),
+        ctx().h, 1, degree, c, C_NULL, npupil, C_NULL, out, 0))
+    return 2 .* (0:npupil-1) ./ npupil, out[:, 1], out[:, 2]
+end
+
 "Power-series coefficients of a row's polynomial; the closure handed to the CPU path is built from the same vector."
 poly(c::Vector{Float64}) = OpticalRayTracing.Polynomial(y -> evalpoly(y, c))
 

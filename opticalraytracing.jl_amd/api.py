@@ -880,6 +880,20 @@ def psf(coef, degree: int, npupil: int = 128, nimg: int = 64, dxi: float = 0.125
     return p[0], float(s[0])
 
 
+def mtf_frequencies(npupil: int):
+    """Spatial frequency of the samples of `mtf`: 2 d / npupil cycles per wavegrad unit, d = 0 .. npupil - 1 (cut-off 2);
+    times |nu| / lambda for cycles per length unit of the prescription."""
+    return 2.0 * np.arange(int(npupil)) / int(npupil)
+
+
+def mtf(coef, degree: int, npupil: int = 128, engine=None):
+    """Sagittal and tangential MTF of the wavefront with the Zernike coefficients `coef` (one vector, as for `psf`) of a field
+    along y, on the GPU (`ort_mtf_f64`): (freq, mtf_sagittal, mtf_tangential) — the modulus of the pupil autocorrelation along
+    x and along y at `mtf_frequencies(npupil)`.  Many bundles, device-resident coefficients or the complex OTF: HipEngine.mtf."""
+    m, _ = _eng(engine).mtf(np.atleast_2d(np.asarray(coef, dtype=np.float64)), degree, npupil)
+    return mtf_frequencies(npupil), m[0, 0], m[0, 1]
+
+
 # ---------------------------------------------------------------------------------------
 # transfer matrix (TransferMatrix.jl)
 # ---------------------------------------------------------------------------------------

@@ -82,7 +82,7 @@ enum { SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, S
        SL_TOFF, SL_TSQ, SL_AGG, SL_RES0, SL_RES1, SL_TAB0, SL_TAB1, SL_TAB2, SL_TAB3,
        SL_SB_FO, SL_SB_REC, SL_SB_MF, SL_SB_MR, SL_SB_TLF, SL_SB_TLR, SL_SB_AIN, SL_SB_AOUT, SL_SB_ENDS, SL_SB_FLAG,
        SL_SB_FIELDS, SL_SB_A, SL_SB_HP, SL_SB_PACK, SL_SB_CEXT, SL_SB_CREV, SL_FTSTATE, SL_FTTICKET, SL_FTERR, SL_FTDONE, SL_FTREADY, SL_DOMAIN, SL_RBSLOPES,
-       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_COUNT };
+       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_MTF_WS, SL_COUNT };
 
 }  // namespace
 
@@ -973,6 +973,15 @@ struct PsfPlan {
     double n2;               // N^2, N = nodes inside the disc
 };
 
+// N: the nodes of the midpoint grid inside the disc
+int64_t psf_node_count(int npupil)
+{
+    int64_t n = 0;
+    for (int j = 0; j < npupil / 2; ++j)                         // one quadrant: the grid is symmetric in both axes
+        for (int k = 0; k < npupil / 2; ++k) n += psf_inside(psf_coord(k, npupil), psf_coord(j, npupil));
+    return 4 * n;
+}
+
 PsfPlan psf_plan(int nb, int npupil, int nimg, int cus)
 {
     PsfPlan pl;
@@ -986,10 +995,8 @@ PsfPlan psf_plan(int nb, int npupil, int nimg, int cus)
     pl.spans = (pl.npanels + pl.span_panels - 1) / pl.span_panels;
     const size_t per_bundle = (size_t)pl.spans * 2 * nimg * nimg * sizeof(double);
     pl.bundles_per_pass = pl.spans == 1 ? nb : (int)std::min<size_t>(std::max<size_t>(kZfWorkspaceBytes / per_bundle, 1), (size_t)nb);
-    int64_t n = 0;
-    for (int j = 0; j < npupil / 2; ++j)                         // one quadrant: the grid is symmetric in both axes
-        for (int k = 0; k < npupil / 2; ++k) n += psf_inside(psf_coord(k, npupil), psf_coord(j, npupil));
-    pl.n2 = (double)(4 * n) * (double)(4 * n);
+    const double n = (double)psf_node_count(npupil);
+    pl.n2 = n * n;
     return pl;
 }
 
@@ -1036,6 +1043,75 @@ int psf_device(ort_ctx* ctx, int nb, int degree, const double* coef, const int32
         if (pl.spans > 1)
             hipLaunchKernelGGL(k_psf_fold, dim3((unsigned)nbb * (unsigned)((plane + kPsfBlock - 1) / kPsfBlock)), dim3(kPsfBlock), 0,
                                ctx->stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return ORT_OK;
+}
+
+// ---- tangential / sagittal OTF and MTF of Zernike wavefronts (k_mtf_*, ort_kernels.hpp) ----
+struct MtfPlan {
+    int G;                   // block diagonals per wave: the instantiation
+    int ngroups;             // groups of 4 G block diagonals, consecutive ones sharing a tile
+    int spans, span_steps;   // workgroups per (bundle, axis, group), k-steps of 4 pupil rows per workgroup
+    int stage_steps, ld;     // k-steps per LDS stage, LDS row stride in doubles
+    size_t lds_bytes;
+    int bundles_per_pass;    // bundles whose offset sums fit the workspace (spans > 1 only)
+};
+
+MtfPlan mtf_plan(int nb, int npupil, int cus)
+{
+    MtfPlan pl;
+    const int nblk = npupil / 16;
+    pl.G = nblk <= 4 ? 1 : nblk <= 8 ? 2 : 4;
+    const int GD = 4 * pl.G;
+    pl.ngroups = std::max(1, (nblk - 1 + GD - 2) / (GD - 1));
+    // The PSF's split: about four workgroups per compute unit.  Few bundles are cut into spans of 16-row panels; from that
+    // many units on a workgroup walks all rows and writes its samples itself: no workspace, one launch.
+    const int64_t target = 4 * (int64_t)std::max(cus, 1), units = (int64_t)nb * 2 * pl.ngroups;
+    const int64_t spans = std::min<int64_t>(std::max<int64_t>((target + units - 1) / units, 1), nblk);
+    const int span_panels = (int)((nblk + spans - 1) / spans);
+    pl.spans = (nblk + span_panels - 1) / span_panels;
+    pl.span_steps = 4 * span_panels;
+    // Row stride: an odd number of 16-double blocks, as zf_ld.  A stage of about 48 KB: fewer barriers at small npupil, one
+    // k-step (65 KB) at npupil = 1024.
+    pl.ld = 16 * (nblk | 1);
+    const size_t step_bytes = (size_t)2 * 4 * pl.ld * sizeof(double);
+    pl.stage_steps = (int)std::min<size_t>(std::max<size_t>(((size_t)48 << 10) / step_bytes, 1), (size_t)pl.span_steps);
+    pl.lds_bytes = std::max(pl.stage_steps * step_bytes, mtf_finish_doubles(pl.G) * sizeof(double));
+    const size_t per_bundle = (size_t)2 * pl.ngroups * pl.spans * GD * kMtfPart * sizeof(double);
+    pl.bundles_per_pass = pl.spans == 1 ? nb : (int)std::min<size_t>(std::max<size_t>(kZfWorkspaceBytes / per_bundle, 1), (size_t)nb);
+    return pl;
+}
+
+// every pointer is a device pointer; info and one of otf, mtf may be null
+int mtf_device(ort_ctx* ctx, int nb, int degree, const double* coef, const int32_t* info, int npupil, double* otf, double* mtf)
+{
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const MtfPlan pl = mtf_plan(nb, npupil, cus);
+    const int GD = 4 * pl.G;
+    MtfArgs a;
+    a.p = PsfArgs{};
+    a.p.spans = pl.spans; a.p.degree = degree; a.p.nterms = degree * (degree + 3) / 2; a.p.npupil = npupil;
+    a.p.coef = coef; a.p.info = info;
+    a.ngroups = pl.ngroups; a.span_steps = pl.span_steps; a.stage_steps = pl.stage_steps; a.ld = pl.ld;
+    a.n = (double)psf_node_count(npupil);
+    a.ws = nullptr; a.otf = otf; a.mtf = mtf;
+    if (pl.spans > 1) {
+        int rc = dev_out<double>(ctx, SL_MTF_WS, (size_t)pl.bundles_per_pass * 2 * pl.ngroups * pl.spans * GD * kMtfPart, &a.ws);
+        if (rc) return rc;
+    }
+    for (int b0 = 0; b0 < nb; b0 += pl.bundles_per_pass) {       // passes share the workspace: stream order keeps them apart
+        const int nbb = std::min(nb - b0, pl.bundles_per_pass);
+        const unsigned units = (unsigned)nbb * 2u * (unsigned)pl.ngroups;
+        const dim3 grid(units * (unsigned)pl.spans), block(kMtfBlock);
+        a.p.b0 = b0;
+        switch (pl.G) {
+        case 1: hipLaunchKernelGGL((k_mtf_accumulate<1>), grid, block, pl.lds_bytes, ctx->stream, a); break;
+        case 2: hipLaunchKernelGGL((k_mtf_accumulate<2>), grid, block, pl.lds_bytes, ctx->stream, a); break;
+        default: hipLaunchKernelGGL((k_mtf_accumulate<4>), grid, block, pl.lds_bytes, ctx->stream, a); break;
+        }
+        if (pl.spans > 1) hipLaunchKernelGGL(k_mtf_fold, dim3(units), block, 0, ctx->stream, a, GD);
         HIP_TRY(hipGetLastError());
     }
     return ORT_OK;
@@ -1273,6 +1349,27 @@ int ort_psf_f64(ort_ctx* ctx, int nb, int degree, const double* coef, const int3
     rc = psf_device(ctx, nb, degree, dcoef, dinfo, npupil, nimg, dxi, dcentre, dpsf, dstrehl); if (rc) return rc;
     if (psf) { rc = from_device<double>(ctx, psf, dpsf, (size_t)nb * plane); if (rc) return rc; }
     rc = from_device<double>(ctx, strehl, dstrehl, (size_t)nb); if (rc) return rc;      // Strehl only: 8 bytes per bundle come back
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ORT_OK;
+}
+
+int ort_mtf_f64(ort_ctx* ctx, int nb, int degree, const double* coef, const int32_t* info, int npupil, double* otf, double* mtf,
+                unsigned flags)
+{
+    int rc = check_ctx(ctx); if (rc) return rc;
+    if (nb <= 0 || !coef || (!otf && !mtf)) return fail(ORT_EINVAL, "bad mtf arguments");
+    if (degree < 1 || degree > kZfMaxDegree) return fail(ORT_EINVAL, "mtf: degree %d outside 1..%d", degree, kZfMaxDegree);
+    if (npupil < 32 || npupil > 1024 || npupil % 16) return fail(ORT_EINVAL, "mtf: npupil %d is not a multiple of 16 in 32..1024", npupil);
+    if ((flags & ORT_DEVICE_PTRS)) return mtf_device(ctx, nb, degree, coef, info, npupil, otf, mtf);
+    const size_t nterms = (size_t)(degree * (degree + 3) / 2), curves = (size_t)nb * 2 * (size_t)npupil;
+    const double* dcoef; const int32_t* dinfo = nullptr; double *dotf = nullptr, *dmtf = nullptr;
+    rc = to_device<double>(ctx, SL_IN0, coef, (size_t)nb * nterms, &dcoef); if (rc) return rc;
+    if (info) { rc = to_device<int32_t>(ctx, SL_IN1, info, (size_t)nb, &dinfo); if (rc) return rc; }
+    if (otf) { rc = dev_out<double>(ctx, SL_OUT0, 2 * curves, &dotf); if (rc) return rc; }
+    if (mtf) { rc = dev_out<double>(ctx, SL_OUT1, curves, &dmtf); if (rc) return rc; }
+    rc = mtf_device(ctx, nb, degree, dcoef, dinfo, npupil, dotf, dmtf); if (rc) return rc;
+    if (otf) { rc = from_device<double>(ctx, otf, dotf, 2 * curves); if (rc) return rc; }
+    if (mtf) { rc = from_device<double>(ctx, mtf, dmtf, curves); if (rc) return rc; }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ORT_OK;
 }

@@ -3144,6 +3144,204 @@ __global__ ORT_ZF_FN __launch_bounds__(kPsfBlock) void k_psf_strehl(PsfArgs a)
     if (tid == 0) a.strehl[b] = ok ? psf_intensity(sr, si, a.n2) : __builtin_nan("");
 }
 
+
+// ------------------------------------------------------------------------------------
+// Tangential and sagittal OTF / MTF of Zernike wavefronts on the device (ort_mtf_f64, include/ort.h).
+//
+// With P the pupil field of ort_psf_f64 (centre 0), the OTF along x is the autocorrelation
+//     H_0(d) = (1 / N) sum_{j,k} P[j][k + d] conj(P[j][k]),      d = 0 .. npupil - 1,
+// and H_1 the same for the transposed pupil.  N H_0(d) is the sum of the d-th sub-diagonal of the Hermitian Gram matrix
+// G[a][c] = sum_j P[j][a] conj(P[j][c]).  G is never formed: every 16 x 16 tile (I, J) with the same D = I - J >= 0 accumulates
+// into ONE complex accumulator tile per block diagonal D, npupil / 16 of them per bundle and axis.
+//
+//   k_mtf_accumulate<G>     a workgroup owns (bundle, axis, a group of 4 G consecutive block diagonals, a span of pupil rows).
+//                           All 256 threads build a stage of pupil rows into LDS, row-major, real and imaginary plane apart,
+//                           only the column blocks that meet the disc.  Per k-step of 4 rows lane l loads
+//                           P[j0 + l / 16][16 I + l % 16]: the A operand for block row I and the B operand for block column I
+//                           (as in k_zfit_accumulate; no transposed copy).  A wave owns G diagonals — dealt back and forth,
+//                           w, 7 - w, 8 + w, 15 - w, so that the waves' tile counts are equal — and walks J once per k-step,
+//                           keeping c_J, s_J, -s_J while it serves them:  Re += c_I c_J + s_I s_J,  Im += s_I c_J + c_I (-s_J).
+//                           Then each accumulator tile goes through a 4 KB LDS scratch of its wave and 62 lanes sum its 31
+//                           offsets r - c (real, imaginary) in column order.  One span: thread d adds the offset sums of its
+//                           two tiles (16 D + r - c = d: tile D for r >= c, tile D + 1 for r < c), divides by N and writes.
+//                           Several spans: the offset sums (not the tiles: 62 numbers per tile instead of 512) go plainly to
+//                           a workspace slot.
+//   k_mtf_fold              a unit's slots summed in span order, then the same finish
+//
+// Groups.  Sample block D needs tiles D and D + 1, so consecutive groups overlap by one tile: group g holds the tiles
+// 15 g .. 15 g + 15 (G = 4) and writes the sample blocks 15 g .. 15 g + 14; the last one also writes its last block, whose
+// neighbour does not exist.  Axis 1 is the same kernel with the node's (x, y) swapped: H_1 of P is H_0 of P^T.
+// ------------------------------------------------------------------------------------
+constexpr int kMtfBlock = 256;                // 4 waves
+constexpr int kMtfOffsets = 31;               // r - c = -15 .. 15 of a 16 x 16 tile
+constexpr int kMtfPart = 2 * kMtfOffsets;     // doubles per tile that leave the accumulate kernel
+
+struct MtfArgs {
+    PsfArgs p;                                // b0, spans, degree, nterms, npupil, coef, info as for the PSF; centre = null
+    int ngroups, span_steps, stage_steps, ld; // groups of diagonals; k-steps per span and per LDS stage; LDS row stride in doubles
+    double n;                                 // N
+    double* ws;                               // [bundle of the pass][axis][group][span][4 G][31][2]
+    double *otf, *mtf;                        // [nb][2][npupil][2] or null, [nb][2][npupil] or null
+};
+
+// Doubles of dynamic LDS k_mtf_accumulate<G> needs: the stage's two planes, later reused as 4 tile scratches + the offset sums.
+ORT_ZF_FN __host__ __device__ constexpr int mtf_finish_doubles(int G) { return 4 * 512 + 4 * G * kMtfPart; }
+
+// The row of [j0, j0 + rows) nearest the grid's centre, and the first column block that meets the disc on that row (the last
+// one is its mirror image).  Both uniform over the workgroup.
+ORT_ZF_FN __device__ __forceinline__ int mtf_nearest_row(int j0, int rows, int npupil)
+{
+    const int half = npupil / 2;
+    return j0 + rows - 1 < half ? j0 + rows - 1 : (j0 > half ? j0 : half);
+}
+ORT_ZF_FN __device__ __forceinline__ int mtf_first_block(int jn, int npupil)
+{
+    const double y = psf_coord(jn, npupil);
+    int J = 0;
+    while (J < npupil / 32 - 1 && !psf_inside(psf_coord(psf_nearest(16 * J, npupil), npupil), y)) ++J;
+    return J;
+}
+
+// hypot in plain IEEE operations: the corrected algorithm of C. F. Borges, "An improved algorithm for hypot(a, b)" (2019),
+// as the GNU C library evaluates it without fused multiply-add — so that mtf is bit for bit what a host caller gets from
+// hypot() of the two numbers in otf.  |H| <= 1: the branch for huge arguments is not needed.
+ORT_ZF_FN __device__ __forceinline__ double mtf_hypot_core(double ax, double ay)
+{
+    double h = sqrt(ax * ax + ay * ay), t1, t2;
+    if (h <= 2.0 * ay) {
+        const double delta = h - ay;
+        t1 = ax * (2.0 * delta - ax);
+        t2 = (delta - 2.0 * (ax - ay)) * delta;
+    } else {
+        const double delta = h - ax;
+        t1 = 2.0 * delta * (ax - 2.0 * ay);
+        t2 = (4.0 * delta - ay) * ay + delta * delta;
+    }
+    return h - (t1 + t2) / (2.0 * h);
+}
+ORT_ZF_FN __device__ __forceinline__ double mtf_hypot(double x, double y)
+{
+    x = fabs(x); y = fabs(y);
+    const double ax = x < y ? y : x, ay = x < y ? x : y;
+    if (ax >= ay / 0x1p-54) return ax + ay;
+    if (ay < 0x1p-459) return mtf_hypot_core(ax / 0x1p-600, ay / 0x1p-600) * 0x1p-600;
+    return mtf_hypot_core(ax, ay);
+}
+
+// Thread tid's sample of the unit (bundle b, axis, group g) from the offset sums of `parts` slots of stride `stride`,
+// added in slot order: sample block t of the group, sample m of the block.
+ORT_ZF_FN __device__ __forceinline__ void mtf_finish(const MtfArgs& a, int GD, int b, int axis, int g, bool ok, const double* part,
+                                                     int parts, size_t stride, int tid)
+{
+    const int t = tid >> 4, m = tid & 15, D0 = g * (GD - 1), D = D0 + t, nblk = a.p.npupil / 16;
+    if (t >= GD || D >= nblk || (t == GD - 1 && D0 + GD < nblk)) return;       // the next group writes its first block
+    double re = 0.0, im = 0.0;
+    for (int s = 0; s < parts; ++s) {
+        const double* q = part + s * stride;
+        re += q[(t * kMtfOffsets + 15 + m) * 2]; im += q[(t * kMtfOffsets + 15 + m) * 2 + 1];
+        if (m > 0 && t + 1 < GD) { re += q[((t + 1) * kMtfOffsets + m - 1) * 2]; im += q[((t + 1) * kMtfOffsets + m - 1) * 2 + 1]; }
+    }
+    const double nan = __builtin_nan("");
+    re = ok ? re / a.n : nan; im = ok ? im / a.n : nan;
+    const size_t o = ((size_t)b * 2 + axis) * a.p.npupil + 16 * D + m;
+    if (a.otf) { a.otf[2 * o] = re; a.otf[2 * o + 1] = im; }
+    if (a.mtf) a.mtf[o] = ok ? mtf_hypot(re, im) : nan;
+}
+
+extern __shared__ double mtf_lds[];
+
+// Grid: bundles of the pass x 2 axes x groups x spans.  Dynamic LDS: max(2 x 4 stage_steps x ld, mtf_finish_doubles(G)) doubles.
+template <int G>
+__global__ ORT_ZF_FN __launch_bounds__(kMtfBlock) void k_mtf_accumulate(MtfArgs a)
+{
+    constexpr int GD = 4 * G;
+    __shared__ PsfShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int u = blockIdx.x;
+    const int span = u % a.p.spans; u /= a.p.spans;
+    const int g = u % a.ngroups; u /= a.ngroups;
+    const int axis = u & 1, bl = u >> 1, b = a.p.b0 + bl;
+    const int npupil = a.p.npupil, nblk = npupil / 16, half = npupil / 2, ld = a.ld, D0 = g * (GD - 1);
+    const int s_lo = span * a.span_steps, s_hi = min(s_lo + a.span_steps, npupil / 4);
+    const bool ok = psf_prepare(sh, a.p, b, tid);
+    double* re = mtf_lds;
+    double* im = mtf_lds + 4 * a.stage_steps * ld;
+    int dq[G];                                                   // this wave's diagonals, relative to J
+#pragma unroll
+    for (int q = 0; q < G; ++q) dq[q] = D0 + 4 * q + ((q & 1) ? 3 - wave : wave);
+    zf_d4 Ar[G], Ai[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) { Ar[q] = zf_d4{0.0, 0.0, 0.0, 0.0}; Ai[q] = zf_d4{0.0, 0.0, 0.0, 0.0}; }
+    for (int s0 = ok ? s_lo : s_hi; s0 < s_hi; s0 += a.stage_steps) {
+        const int ns = min(a.stage_steps, s_hi - s0), j0 = 4 * s0, rows = 4 * ns;
+        const int jl = mtf_first_block(mtf_nearest_row(j0, rows, npupil), npupil), wb = nblk - 2 * jl;
+        if (wb - 1 < D0) continue;                               // no tile pair of this group in these rows (uniform)
+        __syncthreads();                                         // the previous stage's readers are done
+        for (int e = tid; e < rows * wb * 16; e += kMtfBlock) {
+            const int ch = e >> 4, r = ch / wb, k = 16 * (jl + ch - r * wb) + (e & 15);
+            const double cu = psf_coord(k, npupil), cv = psf_coord(j0 + r, npupil);
+            double pr, pi;
+            psf_node(sh, a.p.degree, axis ? cv : cu, axis ? cu : cv, &pr, &pi);
+            re[r * ld + k] = pr; im[r * ld + k] = pi;
+        }
+        __syncthreads();
+        for (int ks = 0; ks < ns; ++ks) {
+            const int js = j0 + 4 * ks;                          // 4 rows on one side of the centre: half is a multiple of 8
+            const int lo = mtf_first_block(js + 3 < half ? js + 3 : js, npupil), hi = nblk - 1 - lo;
+            const double* rr = re + (4 * ks + (lane >> 4)) * ld + (lane & 15);
+            const double* ri = im + (4 * ks + (lane >> 4)) * ld + (lane & 15);
+            for (int J = lo; J + dq[0] <= hi; ++J) {             // dq[0] is the wave's smallest
+                const double cJ = rr[16 * J], sJ = ri[16 * J], nsJ = -sJ;
+#pragma unroll
+                for (int q = 0; q < G; ++q) {
+                    const int I = J + dq[q];
+                    if (I > hi) continue;                        // uniform over the wave
+                    const double cI = rr[16 * I], sI = ri[16 * I];
+                    Ar[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cI, cJ, Ar[q], 0, 0, 0);
+                    Ar[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(sI, sJ, Ar[q], 0, 0, 0);
+                    Ai[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(sI, cJ, Ai[q], 0, 0, 0);
+                    Ai[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cI, nsJ, Ai[q], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // Offset sums.  Element (r, c) of a tile is register r / 4 of lane 16 (r % 4) + c (zf_tile_offset).
+    double* scratch = mtf_lds + wave * 512;
+    double* part = mtf_lds + 4 * 512;
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+        __syncthreads();                                         // the stage's, then the previous tile's readers are done
+#pragma unroll
+        for (int v = 0; v < 4; ++v) { scratch[v * 64 + lane] = Ar[q][v]; scratch[256 + v * 64 + lane] = Ai[q][v]; }
+        __syncthreads();
+        if (lane < kMtfPart) {
+            const int o = lane >> 1, off = o - 15;
+            const double* src = scratch + (lane & 1) * 256;
+            double s = 0.0;
+            for (int c = off < 0 ? -off : 0; c <= (off > 0 ? 15 - off : 15); ++c) s += src[zf_tile_offset(c + off, c)];
+            part[(dq[q] - D0) * kMtfPart + lane] = s;
+        }
+    }
+    __syncthreads();
+    if (a.p.spans == 1) mtf_finish(a, GD, b, axis, g, ok, part, 1, 0, tid);
+    else {
+        double* slot = a.ws + (size_t)blockIdx.x * (GD * kMtfPart);
+        for (int e = tid; e < GD * kMtfPart; e += kMtfBlock) slot[e] = part[e];
+    }
+}
+
+// Grid: bundles of the pass x 2 axes x groups; one thread per sample.
+__global__ ORT_ZF_FN __launch_bounds__(kMtfBlock) void k_mtf_fold(MtfArgs a, int GD)
+{
+    int u = blockIdx.x;
+    const int g = u % a.ngroups; u /= a.ngroups;
+    const int axis = u & 1, b = a.p.b0 + (u >> 1);
+    const double c0 = a.p.coef[(size_t)b * a.p.nterms];
+    const bool ok = !(a.p.info && a.p.info[b] != 0) && c0 == c0;
+    const size_t stride = (size_t)GD * kMtfPart;
+    mtf_finish(a, GD, b, axis, g, ok, a.ws + (size_t)blockIdx.x * a.p.spans * stride, a.p.spans, stride, threadIdx.x);
+}
+
 #undef ORT_ZF_FN
 
 }  // namespace ort

@@ -256,6 +256,32 @@ class HipEngine:
                                        None if psf is None else ptr(psf), ptr(strehl), flags))
         return psf, strehl
 
+    # ---- tangential / sagittal OTF and MTF of Zernike wavefronts ----
+    def mtf(self, coef, degree: int, npupil: int, info=None, want_otf: bool = False):
+        """`ort_mtf_f64`: the modulus transfer function [nb][2][npupil] of the wavefronts whose Zernike coefficients are coef
+        [nb][nterms] — the autocorrelation of the pupil field of `psf` along x (axis 0) and along y (axis 1), sample d at
+        2 d / npupil cycles per wavegrad unit (`mtf_frequencies`).  Returns (mtf, otf or None); want_otf = True also gives the
+        complex OTF [nb][2][npupil] (complex128).  Rows with info != 0 or NaN coefficients give NaN.  numpy arrays go through
+        host buffers; torch CUDA tensors (coef, and info when given) stay on the device — the call is asynchronous on the
+        engine's stream and the results are torch tensors."""
+        nb = coef.shape[0]
+        if hasattr(coef, "data_ptr"):
+            import torch
+            otf = torch.empty((nb, 2, npupil, 2), dtype=torch.float64, device=coef.device) if want_otf else None
+            mtf = torch.empty((nb, 2, npupil), dtype=torch.float64, device=coef.device)
+            flags = self.base_flags | _capi.ORT_DEVICE_PTRS
+        else:
+            coef = f64(coef)
+            info = None if info is None else np.ascontiguousarray(info, dtype=np.int32)
+            otf = np.empty((nb, 2, npupil, 2)) if want_otf else None
+            mtf = np.empty((nb, 2, npupil))
+            flags = self.base_flags
+        check(self.ctx.lib.ort_mtf_f64(self.ctx.h, int(nb), int(degree), ptr(coef), None if info is None else ptr(info), int(npupil),
+                                       None if otf is None else ptr(otf), ptr(mtf), flags))
+        if otf is not None:
+            otf = torch.view_as_complex(otf) if hasattr(otf, "data_ptr") else otf.view(np.complex128)[..., 0]
+        return mtf, otf
+
     # ---- meridional: raytrace(surfaces, y, U, RealRay)  RayTracing.jl:145-169 -----------
     def meridional(self, pres: Prescription, y, U, layout_mode: bool = False, isys: int = 0):
         y, U = (np.atleast_1d(f64(a)) for a in (y, U))
