@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64 and ort_mtf_f64: new entry points only, nothing existing moved)
+#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64, ort_mtf_f64 and ort_spot_radii_f64 / _f32: new entry points only, nothing existing moved)
                                       0.4.1: ORT_FT_FUSED (full_trace's second pass inside the trace launch; bit-identical results) and its
                                       testing aid ort_ctx_test_fused_no_scan.  0.4.0: no new entry point; statistics-only full_trace walks tiles per workgroup (results within 1e-12 of
                                       0.3.0's); the device-side aiming loops trace without trigonometric calls only under ORT_FAST_MATH;
@@ -318,6 +318,35 @@ int ort_mtf_f64(ort_ctx *ctx, int nb, int degree, const double *coef /* [nb][nte
                 const int32_t *info /* [nb] or NULL */, int npupil,
                 double *otf /* [nb][2][npupil][2] or NULL */, double *mtf /* [nb][2][npupil] or NULL */,
                 unsigned flags);
+/* Geometric (GEO) and encircled-energy radii of nb full_trace results, the order statistics a spot-diagram report quotes
+ * beside the RMS, without bringing the vectors to the host (no reference counterpart: the reference stops at sigma).
+ *  - ex, ey : [nb][cap] with count[b] valid entries per slab, the layout of ort_full_trace_f64 / _f32 and of
+ *    ort_zernike_fit_f64; entries at index count[b] and beyond are never read (a count[b] > cap is read as cap).
+ *  - with n = count[b]: mu = (sum ex / n, sum ey / n), the centroid of the reference's sigma (src/PupilSampling.jl:169-173);
+ *    q_i = (ex_i - mu_x)^2 + (ey_i - mu_y)^2 in binary64 (the f32 variant promotes each entry first).
+ *  - for fraction f the rank is k = min(n, max(1, ceil(f n))), f n the IEEE double product (double)n * f: a host's
+ *    ceil(f * n) gives the same integer.  radii[b][i] = sqrt(k-th smallest q); f = 1 gives the GEO radius, the distance of
+ *    the farthest ray from the centroid.  centroid[b] = {mu_x, mu_y}.
+ *  - the selection is exact — a radix selection on the bit pattern of q by integer counting, no sort and no floating-point
+ *    atomics: the result is the square root of one of the bundle's own q values, whatever the ties.
+ *  - mu is summed in a fixed order (the slab in chunks of 8192 entries; per thread in index order, a fixed tree, chunks in
+ *    chunk order), the same however the call is cut into workgroups: the same call gives the same bits from run to run, with
+ *    host or device pointers, and on every route — slabs of cap <= 16384 are selected in LDS (one read of ex, ey); larger
+ *    ones recompute q from ex, ey in each of the eight counting passes.
+ *  - count[b] <= 0 (an empty bundle, or the -1 of a faulted look-back / fused full_trace) gives NaN in that bundle's
+ *    outputs; the call still returns ORT_OK.  Inputs are assumed finite: full_trace writes survivors only.
+ * count : [nb]; frac : [nfrac], HOST always (like `bundles` of the grid calls); centroid : [nb][2] or NULL; radii : [nb][nfrac].
+ * count, ex, ey, centroid, radii: host or device pointers per ORT_DEVICE_PTRS, as for ort_zernike_fit_f64.
+ * ORT_EINVAL: nfrac outside 1..8, a fraction outside (0, 1] or NaN, NULL count, ex, ey, frac or radii, cap < 1 or cap >= 2^31
+ * (the counters are 32-bit), nb < 0. */
+int ort_spot_radii_f64(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count,
+                       const double *ex, const double *ey,
+                       int nfrac, const double *frac /* [nfrac], HOST always */,
+                       double *centroid /* [nb][2] or NULL */, double *radii /* [nb][nfrac] */, unsigned flags);
+int ort_spot_radii_f32(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count,
+                       const float *ex, const float *ey,
+                       int nfrac, const double *frac /* [nfrac], HOST always */,
+                       double *centroid /* [nb][2] or NULL */, double *radii /* [nb][nfrac] */, unsigned flags);
 /* Testing aid: shift the context's look-back ticket base against the device counter, the bookkeeping fault that
  * ort_full_trace_* with ORT_FT_LOOKBACK must report (ORT_EHIP; device-pointer callers see count = -1, rms = NaN). */
 int ort_ctx_test_skew_tickets(ort_ctx *ctx, int64_t delta);

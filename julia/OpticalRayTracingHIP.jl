@@ -175,6 +175,29 @@ function mtf(c::Vector{Float64}, degree::Integer; npupil::Integer = 128)
     return 2 .* (0:npupil-1) ./ npupil, out[:, 1], out[:, 2]
 end
 
+"""
+    spot_radii(ε::RealRayError, fractions = [0.5, 0.8, 1.0]) -> (centroid, radii)
+
+Centroid and encircled-energy radii of a `full_trace` result (`ort_spot_radii_f64`): per fraction `f` the radius about the
+centroid that holds `ceil(f * n)` of the `n` rays, an exact order statistic; `f = 1` is the GEO radius.  `Float32` vectors take
+`ort_spot_radii_f32`.  Device-resident slabs of many bundles take the same calls with `DeviceArray` pointers and ORT_DEVICE_PTRS.
+"""
+function spot_radii(ε, fractions::Vector{Float64} = [0.5, 0.8, 1.0])
+    n = length(ε.x); cnt = Int64[n]; c = Vector{Float64}(undef, 2); r = Vector{Float64}(undef, length(fractions))
+    if eltype(ε.x) === Float32
+        x = collect(Float32, ε.x); y = collect(Float32, ε.y)
+        GC.@preserve cnt x y fractions c r check(ccall((:ort_spot_radii_f32, LIB), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Float32}, Ptr{Float32}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32),
+            ctx().h, 1, n, cnt, x, y, length(fractions), fractions, c, r, 0))
+    else
+        x = collect(Float64, ε.x); y = collect(Float64, ε.y)
+        GC.@preserve cnt x y fractions c r check(ccall((:ort_spot_radii_f64, LIB), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, UInt32),
+            ctx().h, 1, n, cnt, x, y, length(fractions), fractions, c, r, 0))
+    end
+    return c, r
+end
+
 "Power-series coefficients of a row's polynomial; the closure handed to the CPU path is built from the same vector."
 poly(c::Vector{Float64}) = OpticalRayTracing.Polynomial(y -> evalpoly(y, c))
 

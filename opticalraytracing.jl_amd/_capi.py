@@ -131,6 +131,8 @@ SIGNATURES = {
     "ort_zernike_fit_f64": (_i, [_p, _i, _l, _p, _p, C.c_double, _p, _p, _p, _p, _i, _p, _p, _p, _u]),
     "ort_psf_f64": (_i, [_p, _i, _i, _p, _p, _i, _i, C.c_double, _p, _p, _p, _u]),
     "ort_mtf_f64": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _u]),
+    "ort_spot_radii_f64": (_i, [_p, _i, _l, _p, _p, _p, _i, _p, _p, _p, _u]),
+    "ort_spot_radii_f32": (_i, [_p, _i, _l, _p, _p, _p, _i, _p, _p, _p, _u]),
     "ort_ctx_test_skew_tickets": (_i, [_p, _l]),
     "ort_ctx_test_fused_no_scan": (_i, [_p, _i]),
     "ort_aim_f64": (_i, [_p, _p, _p, _i, C.POINTER(ort_aim_in), C.POINTER(ort_aim_out), _u]),

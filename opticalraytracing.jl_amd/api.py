@@ -894,6 +894,15 @@ def mtf(coef, degree: int, npupil: int = 128, engine=None):
     return mtf_frequencies(npupil), m[0, 0], m[0, 1]
 
 
+def spot_radii(err: RealRayError, fractions=(0.5, 0.8, 1.0), engine=None):
+    """Centroid and encircled-energy radii of a full_trace result on the GPU (`ort_spot_radii_f64`): (centroid [2],
+    radii [len(fractions)]) — per fraction f the radius about the centroid that holds ceil(f n) of the n rays, an exact order
+    statistic; f = 1 is the GEO radius, the distance of the farthest ray.  Device-resident slabs of many bundles, or Float32
+    vectors: HipEngine.spot_radii."""
+    c, r = _eng(engine).spot_radii(np.atleast_2d(err.x), np.atleast_2d(err.y), [len(err.x)], fractions)
+    return c[0], r[0]
+
+
 # ---------------------------------------------------------------------------------------
 # transfer matrix (TransferMatrix.jl)
 # ---------------------------------------------------------------------------------------

@@ -82,7 +82,7 @@ enum { SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, S
        SL_TOFF, SL_TSQ, SL_AGG, SL_RES0, SL_RES1, SL_TAB0, SL_TAB1, SL_TAB2, SL_TAB3,
        SL_SB_FO, SL_SB_REC, SL_SB_MF, SL_SB_MR, SL_SB_TLF, SL_SB_TLR, SL_SB_AIN, SL_SB_AOUT, SL_SB_ENDS, SL_SB_FLAG,
        SL_SB_FIELDS, SL_SB_A, SL_SB_HP, SL_SB_PACK, SL_SB_CEXT, SL_SB_CREV, SL_FTSTATE, SL_FTTICKET, SL_FTERR, SL_FTDONE, SL_FTREADY, SL_DOMAIN, SL_RBSLOPES,
-       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_MTF_WS, SL_COUNT };
+       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_MTF_WS, SL_SPOT_WS, SL_COUNT };
 
 }  // namespace
 
@@ -1117,6 +1117,101 @@ int mtf_device(ort_ctx* ctx, int nb, int degree, const double* coef, const int32
     return ORT_OK;
 }
 
+// ---- encircled-energy / GEO radii of spots (k_spot_*, ort_kernels.hpp) ----
+struct SpotPlan {
+    char route;              // 'a': slab in LDS; 'b': one workgroup per bundle, q recomputed; 'c': bundles cut into spans
+    int nchunks;             // chunks of kSpotChunk entries per slab
+    int spans, span_chunks;  // route (c): workgroups per bundle, chunks per workgroup
+    size_t lds_bytes;        // route (a): dynamic LDS
+};
+
+// The counts may lie on the device, so the host picks by the slab size: no slab entry beyond cap exists.
+SpotPlan spot_plan(int nb, int64_t cap, int cus)
+{
+    SpotPlan pl;
+    pl.nchunks = (int)((cap + kSpotChunk - 1) / kSpotChunk);
+    pl.spans = 1; pl.span_chunks = pl.nchunks; pl.lds_bytes = 0;
+    const int64_t target = 4 * (int64_t)std::max(cus, 1);       // the PSF's rule: about four workgroups per compute unit
+    if (cap <= kSpotLdsEntries) { pl.route = 'a'; pl.lds_bytes = (size_t)cap * sizeof(double); }
+    else if (nb >= target) pl.route = 'b';
+    else {
+        pl.route = 'c';
+        const int64_t spans = std::min<int64_t>(std::max<int64_t>((target + nb - 1) / nb, 1), pl.nchunks);
+        pl.span_chunks = (int)((pl.nchunks + spans - 1) / spans);
+        pl.spans = (pl.nchunks + pl.span_chunks - 1) / pl.span_chunks;
+    }
+    return pl;
+}
+
+// every pointer but frac is a device pointer; centroid may be null
+template <typename T>
+int spot_radii_device(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const T* ex, const T* ey, int nfrac, const double* frac,
+                      double* centroid, double* radii)
+{
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const SpotPlan pl = spot_plan(nb, cap, cus);
+    SpotArgs<T> a;
+    memset(&a, 0, sizeof a);
+    a.nfrac = nfrac; a.nchunks = pl.nchunks; a.spans = pl.spans; a.span_chunks = pl.span_chunks; a.cap = cap;
+    a.count = count; a.ex = ex; a.ey = ey; a.centroid = centroid; a.radii = radii;
+    for (int i = 0; i < nfrac; ++i) a.frac[i] = frac[i];
+    const dim3 block(kSpotBlock);
+    if (pl.route == 'a') {
+        if (pl.lds_bytes > ((size_t)64 << 10))
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spot_select<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)pl.lds_bytes));
+        hipLaunchKernelGGL((k_spot_select<T, true>), dim3((unsigned)nb), block, pl.lds_bytes, ctx->stream, a);
+    } else if (pl.route == 'b') {
+        hipLaunchKernelGGL((k_spot_select<T, false>), dim3((unsigned)nb), block, 0, ctx->stream, a);
+    } else {
+        // workspace: [chunk sums | mu | states | histograms], every part a multiple of 8 bytes
+        const size_t n_part = (size_t)nb * pl.nchunks * 2, n_mu = (size_t)nb * 2, n_state = (size_t)nb * kSpotPasses;
+        const size_t n_hist = (size_t)nb * kSpotPasses * nfrac * 256;
+        unsigned char* ws = nullptr;
+        int rc = dev_out<unsigned char>(ctx, SL_SPOT_WS, (n_part + n_mu) * sizeof(double) + n_state * sizeof(SpotState) + n_hist * sizeof(unsigned), &ws);
+        if (rc) return rc;
+        a.part = reinterpret_cast<double*>(ws); a.mu = a.part + n_part;
+        a.state = reinterpret_cast<SpotState*>(a.mu + n_mu); a.hist = reinterpret_cast<unsigned*>(a.state + n_state);
+        const dim3 grid((unsigned)nb * (unsigned)pl.spans);
+        hipLaunchKernelGGL(k_spot_zero, dim3((unsigned)std::min<size_t>((n_hist + kSpotBlock - 1) / kSpotBlock, 4096)), block, 0, ctx->stream,
+                           a.hist, n_hist);
+        hipLaunchKernelGGL((k_spot_centroid<T>), grid, block, 0, ctx->stream, a);
+        hipLaunchKernelGGL(k_spot_fold, dim3((unsigned)((nb + kSpotBlock - 1) / kSpotBlock)), block, 0, ctx->stream, nb, pl.nchunks, cap, count,
+                           (const double*)a.part, a.mu, centroid);
+        for (int pass = 0; pass <= kSpotPasses; ++pass)          // stream order: pass p + 1 reads what pass p counted
+            hipLaunchKernelGGL((k_spot_select_span<T>), grid, block, 0, ctx->stream, a, pass);
+    }
+    HIP_TRY(hipGetLastError());
+    return ORT_OK;
+}
+
+template <typename T>
+int spot_radii_entry(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const T* ex, const T* ey, int nfrac, const double* frac,
+                     double* centroid, double* radii, unsigned flags)
+{
+    int rc = check_ctx(ctx); if (rc) return rc;
+    if (nb < 0 || cap < 1 || !count || !ex || !ey || !frac || !radii) return fail(ORT_EINVAL, "bad spot_radii arguments");
+    if (nfrac < 1 || nfrac > kSpotMaxFrac) return fail(ORT_EINVAL, "spot_radii: nfrac %d outside 1..%d", nfrac, kSpotMaxFrac);
+    for (int i = 0; i < nfrac; ++i)
+        if (!(frac[i] > 0.0 && frac[i] <= 1.0)) return fail(ORT_EINVAL, "spot_radii: fraction %d (%g) outside (0, 1]", i, frac[i]);
+    if (cap > 0x7fffffffLL) return fail(ORT_EINVAL, "spot_radii: cap %lld exceeds the 32-bit counters", (long long)cap);
+    if (nb == 0) return ORT_OK;
+    if ((flags & ORT_DEVICE_PTRS)) return spot_radii_device<T>(ctx, nb, cap, count, ex, ey, nfrac, frac, centroid, radii);
+    const size_t n = (size_t)nb * (size_t)cap;
+    const int64_t* dcount; const T *dex, *dey; double *dcen = nullptr, *drad;
+    rc = to_device<int64_t>(ctx, SL_IN0, count, (size_t)nb, &dcount); if (rc) return rc;
+    rc = to_device<T>(ctx, SL_IN2, ex, n, &dex); if (rc) return rc;
+    rc = to_device<T>(ctx, SL_IN3, ey, n, &dey); if (rc) return rc;
+    if (centroid) { rc = dev_out<double>(ctx, SL_OUT0, (size_t)nb * 2, &dcen); if (rc) return rc; }
+    rc = dev_out<double>(ctx, SL_OUT1, (size_t)nb * nfrac, &drad); if (rc) return rc;
+    rc = spot_radii_device<T>(ctx, nb, cap, dcount, dex, dey, nfrac, frac, dcen, drad); if (rc) return rc;
+    if (centroid) { rc = from_device<double>(ctx, centroid, dcen, (size_t)nb * 2); if (rc) return rc; }
+    rc = from_device<double>(ctx, radii, drad, (size_t)nb * nfrac); if (rc) return rc;       // 8 (2 + nfrac) bytes per bundle come back
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ORT_OK;
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -1372,6 +1467,18 @@ int ort_mtf_f64(ort_ctx* ctx, int nb, int degree, const double* coef, const int3
     if (mtf) { rc = from_device<double>(ctx, mtf, dmtf, curves); if (rc) return rc; }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ORT_OK;
+}
+
+int ort_spot_radii_f64(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const double* ex, const double* ey, int nfrac,
+                       const double* frac, double* centroid, double* radii, unsigned flags)
+{
+    return spot_radii_entry<double>(ctx, nb, cap, count, ex, ey, nfrac, frac, centroid, radii, flags);
+}
+
+int ort_spot_radii_f32(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const float* ex, const float* ey, int nfrac,
+                       const double* frac, double* centroid, double* radii, unsigned flags)
+{
+    return spot_radii_entry<float>(ctx, nb, cap, count, ex, ey, nfrac, frac, centroid, radii, flags);
 }
 
 int ort_device_upload(ort_ctx* ctx, void* dst, const void* src, size_t bytes)

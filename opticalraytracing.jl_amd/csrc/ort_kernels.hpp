@@ -3342,6 +3342,345 @@ __global__ ORT_ZF_FN __launch_bounds__(kMtfBlock) void k_mtf_fold(MtfArgs a, int
     mtf_finish(a, GD, b, axis, g, ok, a.ws + (size_t)blockIdx.x * a.p.spans * stride, a.p.spans, stride, threadIdx.x);
 }
 
+
+// ------------------------------------------------------------------------------------
+// Encircled-energy and GEO radii of spots on the device (ort_spot_radii_f64 / _f32, include/ort.h).
+//
+// radii[b][r] = sqrt of the k_r-th smallest q_i = (ex_i - mu_x)^2 + (ey_i - mu_y)^2 of bundle b, k_r = ceil(f_r n) clamped to
+// 1 .. n.  An exact multi-rank radix selection: a non-negative binary64 orders as its 64-bit pattern, so the k-th smallest key
+// is found most significant byte first in eight counting passes.  Every rank carries (prefix so far, rank remaining among the
+// keys with that prefix); in a pass a key whose high bits equal a rank's prefix bumps bin (next byte) of that rank's 256-bin
+// histogram — 32-bit integer LDS atomics, nothing else — and then one wave per rank takes a prefix sum over the 256 bins with
+// wave shuffles, picks the bin that holds the rank, appends it to the prefix and reduces the rank.  After eight passes the
+// prefix IS the key.  Ties need no care: equal keys fall into the same bin in every pass.  No key array goes to HBM.
+//   ranks with the same prefix (all of them in the first passes) share ONE histogram, the lowest such rank's (SpotState::rep):
+//   a key is counted once per distinct prefix, not once per rank;
+//   a wave whose matching keys all fall into one bin (the rule while the prefix is still inside the exponent) adds their
+//   count with one atomic.
+//
+// The centroid's summation order is fixed and the same on every route: the bundle in chunks of kSpotChunk entries; in a chunk
+// thread t adds entries t, t + 512, .. in index order, the wave's 64 sums meet in an xor butterfly (a + b on both lanes: the
+// same bits), the 8 wave sums are added in wave order; chunk sums are added in chunk order; one division by n.
+//
+//   k_spot_select<T, true>    route (a), cap <= kSpotLdsEntries: one workgroup per bundle reads ex, ey ONCE (ex into dynamic
+//                             LDS, ey into registers), forms mu, overwrites the LDS copy with q and runs the eight passes on it
+//   k_spot_select<T, false>   route (b), larger slabs, >= 4 bundles per compute unit: the same launch shape, q recomputed from
+//                             ex, ey, mu in every pass
+//   route (c), few large slabs, a bundle cut into spans of whole chunks, about four workgroups per compute unit:
+//   k_spot_centroid<T>        chunk sums, stored plainly to a workspace slot;  k_spot_fold adds them in chunk order
+//   k_spot_select_span<T>     launched for pass 0 .. 8.  Head (pass > 0): every workgroup reads the state the previous launch
+//                             counted with and scans the bundle's histogram of that pass itself (256 nfrac counters: L2 hits);
+//                             span 0 records the new state.  Body (pass < 8): the span's keys into an LDS histogram, then its
+//                             non-zero counters onto the bundle's histogram of this pass in the workspace with integer global
+//                             atomics — exact, order-independent.  Pass 8 is the head alone: sqrt and store.
+//                             Each pass has its own histogram in the workspace, all zeroed by k_spot_zero up front.
+// ------------------------------------------------------------------------------------
+constexpr int kSpotBlock = 512;               // 8 waves: one per rank in the digit choice
+constexpr int kSpotWaves = kSpotBlock / 64;
+constexpr int kSpotMaxFrac = 8;
+constexpr int kSpotPasses = 8;                // 8-bit digits of a 64-bit key
+constexpr int kSpotChunk = 8192;              // entries per step of the centroid's summation order; the unit spans are made of
+constexpr int kSpotPer = kSpotChunk / kSpotBlock;         // entries per thread and chunk
+constexpr int kSpotLdsEntries = 16384;        // route (a): q of a whole slab in 128 KB of dynamic LDS, beside 8.3 KB static
+constexpr int kSpotLdsPer = kSpotLdsEntries / kSpotBlock; // ey values a thread of route (a) keeps in registers
+
+struct SpotState {
+    unsigned long long pre[kSpotMaxFrac];     // the key's bytes decided so far, the rest zero
+    unsigned rem[kSpotMaxFrac];               // 1-based rank among the keys that carry the prefix
+    int rep[kSpotMaxFrac];                    // lowest rank with the same prefix: the owner of the shared histogram
+};
+
+struct SpotShared {
+    unsigned hist[kSpotMaxFrac * 256];
+    SpotState st;
+    double red[2 * kSpotWaves];
+};
+
+template <typename T>
+struct SpotArgs {
+    int nfrac, nchunks, spans, span_chunks;   // chunks per slab (of cap entries); route (c): workgroups per bundle, chunks per workgroup
+    int64_t cap;
+    const int64_t* count;
+    const T *ex, *ey;
+    double frac[kSpotMaxFrac];
+    double *centroid, *radii;                 // [nb][2] or null, [nb][nfrac]
+    double *part, *mu;                        // route (c) workspace: [nb][nchunks][2] chunk sums, [nb][2]
+    SpotState* state;                         // [nb][kSpotPasses]: the state pass p counted with
+    unsigned* hist;                           // [nb][kSpotPasses][nfrac][256]
+};
+
+// count[b] clamped to the slab: nothing at or beyond index min(count, cap) is read
+ORT_ZF_FN __device__ __forceinline__ int64_t spot_entries(const int64_t* __restrict__ count, int b, int64_t cap)
+{
+    const int64_t n = count[b];
+    return n < cap ? n : cap;
+}
+
+// k = min(n, max(1, ceil(f n))) of rank `r`; the fractions are kernel arguments, selected without an indexed copy
+template <typename T>
+ORT_ZF_FN __device__ __forceinline__ unsigned spot_rank(const SpotArgs<T>& a, int r, int64_t n)
+{
+    double f = a.frac[0];
+#pragma unroll
+    for (int i = 1; i < kSpotMaxFrac; ++i) f = r == i ? a.frac[i] : f;
+    const double c = ceil((double)n * f);
+    int64_t k = (int64_t)c;
+    k = k < 1 ? 1 : k;
+    return (unsigned)(k < n ? k : n);
+}
+
+template <typename T>
+ORT_ZF_FN __device__ __forceinline__ void spot_init_state(SpotState& st, const SpotArgs<T>& a, int64_t n, int tid)
+{
+    if (tid < a.nfrac) { st.pre[tid] = 0ull; st.rem[tid] = spot_rank(a, tid, n); st.rep[tid] = 0; }
+}
+
+// This thread's share of the chunk that starts at entry lo
+template <typename T>
+ORT_ZF_FN __device__ __forceinline__ void spot_chunk_partial(const T* __restrict__ ex, const T* __restrict__ ey, int64_t lo, int64_t n,
+                                                             int tid, double& sx, double& sy)
+{
+    sx = 0.0; sy = 0.0;
+#pragma unroll 4
+    for (int j = 0; j < kSpotPer; ++j) {
+        const int64_t i = lo + j * kSpotBlock + tid;
+        if (i < n) { sx += (double)ex[i]; sy += (double)ey[i]; }
+    }
+}
+
+// The threads' shares of a chunk -> the chunk's sums, in every thread
+ORT_ZF_FN __device__ __forceinline__ void spot_tree(double& sx, double& sy, double* red, int tid)
+{
+    for (int o = 32; o > 0; o >>= 1) { sx += __shfl_xor(sx, o); sy += __shfl_xor(sy, o); }
+    __syncthreads();                                             // the previous chunk's readers are done
+    if ((tid & 63) == 0) { red[2 * (tid >> 6)] = sx; red[2 * (tid >> 6) + 1] = sy; }
+    __syncthreads();
+    sx = 0.0; sy = 0.0;
+    for (int w = 0; w < kSpotWaves; ++w) { sx += red[2 * w]; sy += red[2 * w + 1]; }
+}
+
+template <typename T>
+ORT_ZF_FN __device__ __forceinline__ unsigned long long spot_key(T x, T y, double mux, double muy)
+{
+    const double dx = (double)x - mux, dy = (double)y - muy;
+    return (unsigned long long)__double_as_longlong(dx * dx + dy * dy);
+}
+
+// One key per lane into the histograms of the ranks whose prefix it carries.  Called by whole waves (valid = false past the end).
+ORT_ZF_FN __device__ __forceinline__ void spot_bump(SpotShared& sh, int nfrac, unsigned long long himask, int shift,
+                                                    unsigned long long key, bool valid, int lane)
+{
+    const unsigned d = (unsigned)(key >> shift) & 255u;
+    for (int r = 0; r < nfrac; ++r) {
+        if (sh.st.rep[r] != r) continue;                         // counted by the rank it shares a prefix with
+        const bool m = valid && ((key ^ sh.st.pre[r]) & himask) == 0ull;
+        const unsigned long long bal = __ballot(m);
+        if (bal == 0ull) continue;
+        const int leader = __ffsll((long long)bal) - 1;
+        const unsigned dl = (unsigned)__shfl((int)d, leader);
+        if (__all(!m || d == dl)) { if (lane == leader) atomicAdd(&sh.hist[r * 256 + dl], (unsigned)__popcll(bal)); }
+        else if (m) atomicAdd(&sh.hist[r * 256 + d], 1u);
+    }
+}
+
+// The digit choice: wave w serves rank w.  hist: [rank][256], in LDS or in the workspace.
+ORT_ZF_FN __device__ __forceinline__ void spot_choose(SpotState& st, const unsigned* hist, int nfrac, int shift, int wave, int lane)
+{
+    for (int r = wave; r < nfrac; r += kSpotWaves) {
+        const unsigned* h = hist + st.rep[r] * 256 + 4 * lane;
+        const unsigned c0 = h[0], c1 = h[1], c2 = h[2], c3 = h[3], s = c0 + c1 + c2 + c3, k = st.rem[r];
+        unsigned inc = s;
+        for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+        const unsigned before = inc - s;
+        if (k > before && k <= inc) {                            // exactly one lane: 1 <= k <= the keys with this prefix
+            unsigned left = k - before, d = 4u * lane;
+            if (left > c0) { left -= c0; ++d; if (left > c1) { left -= c1; ++d; if (left > c2) { left -= c2; ++d; } } }
+            st.pre[r] |= (unsigned long long)d << shift;
+            st.rem[r] = left;
+        }
+    }
+}
+
+// after the choice: which ranks still share a prefix
+ORT_ZF_FN __device__ __forceinline__ void spot_regroup(SpotState& st, int nfrac, int tid)
+{
+    if (tid < nfrac) {
+        int rep = tid;
+        for (int r = tid - 1; r >= 0; --r) rep = st.pre[r] == st.pre[tid] ? r : rep;
+        st.rep[tid] = rep;
+    }
+}
+
+ORT_ZF_FN __device__ __forceinline__ unsigned long long spot_himask(int pass) { return pass ? ~0ull << (64 - 8 * pass) : 0ull; }
+
+extern __shared__ double spot_lds[];
+
+// Routes (a) and (b).  Grid: bundles.  Dynamic LDS (LDSQ): min(cap, kSpotLdsEntries) doubles.
+template <typename T, bool LDSQ>
+__global__ ORT_ZF_FN __launch_bounds__(kSpotBlock) void k_spot_select(SpotArgs<T> a)
+{
+    __shared__ SpotShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), b = blockIdx.x, nfrac = a.nfrac;
+    const int64_t n = spot_entries(a.count, b, a.cap);
+    if (n <= 0) {                                                // empty, or the -1 of a faulted full_trace
+        if (tid < 2 && a.centroid) a.centroid[2 * (size_t)b + tid] = __builtin_nan("");
+        if (tid < nfrac) a.radii[(size_t)b * nfrac + tid] = __builtin_nan("");
+        return;
+    }
+    const T* __restrict__ ex = a.ex + (size_t)b * a.cap;
+    const T* __restrict__ ey = a.ey + (size_t)b * a.cap;
+    const int nch = (int)((n + kSpotChunk - 1) / kSpotChunk);
+    double* q = spot_lds;
+    double yr[LDSQ ? kSpotLdsPer : 1];
+    double SX = 0.0, SY = 0.0;
+    if constexpr (LDSQ) {
+#pragma unroll
+        for (int c = 0; c < kSpotLdsEntries / kSpotChunk; ++c) {
+            double sx = 0.0, sy = 0.0;
+#pragma unroll
+            for (int j = 0; j < kSpotPer; ++j) {
+                const int i = (c * kSpotPer + j) * kSpotBlock + tid;
+                double y = 0.0;
+                if (i < n) { const double x = (double)ex[i]; y = (double)ey[i]; sx += x; sy += y; q[i] = x; }
+                yr[c * kSpotPer + j] = y;
+            }
+            if (c < nch) { spot_tree(sx, sy, sh.red, tid); SX += sx; SY += sy; }     // uniform
+        }
+    } else {
+        for (int c = 0; c < nch; ++c) {
+            double sx, sy;
+            spot_chunk_partial(ex, ey, (int64_t)c * kSpotChunk, n, tid, sx, sy);
+            spot_tree(sx, sy, sh.red, tid);
+            SX += sx; SY += sy;
+        }
+    }
+    const double mux = SX / (double)n, muy = SY / (double)n;
+    if (tid == 0 && a.centroid) { a.centroid[2 * (size_t)b] = mux; a.centroid[2 * (size_t)b + 1] = muy; }
+    if constexpr (LDSQ) {                                        // a thread meets its own entries only: no barrier
+#pragma unroll
+        for (int j = 0; j < kSpotLdsPer; ++j) {
+            const int i = j * kSpotBlock + tid;
+            if (i < n) { const double dx = q[i] - mux, dy = yr[j] - muy; q[i] = dx * dx + dy * dy; }
+        }
+    }
+    spot_init_state(sh.st, a, n, tid);
+    for (int p = 0; p < kSpotPasses; ++p) {
+        const int shift = 56 - 8 * p;
+        const unsigned long long himask = spot_himask(p);
+        for (int e = tid; e < nfrac * 256; e += kSpotBlock) sh.hist[e] = 0u;
+        __syncthreads();                                         // zeroed counters; the state of this pass
+        for (int64_t base = 0; base < n; base += kSpotBlock) {
+            const int64_t i = base + tid;
+            unsigned long long key = 0ull;
+            if (i < n) {
+                if constexpr (LDSQ) key = (unsigned long long)__double_as_longlong(q[i]);
+                else key = spot_key(ex[i], ey[i], mux, muy);
+            }
+            spot_bump(sh, nfrac, himask, shift, key, i < n, lane);
+        }
+        __syncthreads();
+        spot_choose(sh.st, sh.hist, nfrac, shift, wave, lane);
+        __syncthreads();
+        spot_regroup(sh.st, nfrac, tid);
+    }
+    __syncthreads();
+    if (tid < nfrac) a.radii[(size_t)b * nfrac + tid] = sqrt(__longlong_as_double((long long)sh.st.pre[tid]));
+}
+
+// Route (c).  Grid: bundles x spans.  A chunk's sums go plainly to their workspace slot.
+template <typename T>
+__global__ ORT_ZF_FN __launch_bounds__(kSpotBlock) void k_spot_centroid(SpotArgs<T> a)
+{
+    __shared__ double red[2 * kSpotWaves];
+    const int tid = threadIdx.x, b = blockIdx.x / a.spans, span = blockIdx.x - b * a.spans;
+    const int64_t n = spot_entries(a.count, b, a.cap);
+    const T* __restrict__ ex = a.ex + (size_t)b * a.cap;
+    const T* __restrict__ ey = a.ey + (size_t)b * a.cap;
+    const int c1 = min((span + 1) * a.span_chunks, a.nchunks);
+    for (int c = span * a.span_chunks; c < c1 && (int64_t)c * kSpotChunk < n; ++c) {
+        double sx, sy;
+        spot_chunk_partial(ex, ey, (int64_t)c * kSpotChunk, n, tid, sx, sy);
+        spot_tree(sx, sy, red, tid);
+        if (tid == 0) { double* p = a.part + 2 * ((size_t)b * a.nchunks + c); p[0] = sx; p[1] = sy; }
+    }
+}
+
+// One thread per bundle: the chunk sums in chunk order.
+__global__ ORT_ZF_FN __launch_bounds__(kSpotBlock) void k_spot_fold(int nb, int nchunks, int64_t cap, const int64_t* __restrict__ count,
+                                                                   const double* __restrict__ part, double* __restrict__ mu,
+                                                                   double* __restrict__ centroid)
+{
+    const int b = blockIdx.x * kSpotBlock + threadIdx.x;
+    if (b >= nb) return;
+    const int64_t n = spot_entries(count, b, cap);
+    double mx = __builtin_nan(""), my = mx;
+    if (n > 0) {
+        const double* p = part + 2 * (size_t)b * nchunks;
+        double SX = 0.0, SY = 0.0;
+        for (int c = 0; (int64_t)c * kSpotChunk < n; ++c) { SX += p[2 * c]; SY += p[2 * c + 1]; }
+        mx = SX / (double)n; my = SY / (double)n;
+    }
+    mu[2 * (size_t)b] = mx; mu[2 * (size_t)b + 1] = my;
+    if (centroid) { centroid[2 * (size_t)b] = mx; centroid[2 * (size_t)b + 1] = my; }
+}
+
+__global__ ORT_ZF_FN __launch_bounds__(kSpotBlock) void k_spot_zero(unsigned* __restrict__ p, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * kSpotBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kSpotBlock) p[i] = 0u;
+}
+
+// Route (c).  Grid: bundles x spans, launched for pass = 0 .. kSpotPasses on one stream.
+template <typename T>
+__global__ ORT_ZF_FN __launch_bounds__(kSpotBlock) void k_spot_select_span(SpotArgs<T> a, int pass)
+{
+    __shared__ SpotShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), nfrac = a.nfrac;
+    const int b = blockIdx.x / a.spans, span = blockIdx.x - b * a.spans;
+    const int64_t n = spot_entries(a.count, b, a.cap);
+    if (n <= 0) {
+        if (pass == kSpotPasses && span == 0 && tid < nfrac) a.radii[(size_t)b * nfrac + tid] = __builtin_nan("");
+        return;
+    }
+    const size_t hist_stride = (size_t)nfrac * 256;
+    if (pass == 0) spot_init_state(sh.st, a, n, tid);
+    else {
+        const SpotState* prev = a.state + (size_t)b * kSpotPasses + pass - 1;
+        if (tid < nfrac) { sh.st.pre[tid] = prev->pre[tid]; sh.st.rem[tid] = prev->rem[tid]; sh.st.rep[tid] = prev->rep[tid]; }
+        __syncthreads();
+        spot_choose(sh.st, a.hist + ((size_t)b * kSpotPasses + pass - 1) * hist_stride, nfrac, 64 - 8 * pass, wave, lane);
+        __syncthreads();
+        spot_regroup(sh.st, nfrac, tid);
+    }
+    for (int e = tid; e < nfrac * 256; e += kSpotBlock) sh.hist[e] = 0u;
+    __syncthreads();
+    if (pass == kSpotPasses) {
+        if (span == 0 && tid < nfrac) a.radii[(size_t)b * nfrac + tid] = sqrt(__longlong_as_double((long long)sh.st.pre[tid]));
+        return;
+    }
+    if (span == 0 && tid < nfrac) {
+        SpotState* now = a.state + (size_t)b * kSpotPasses + pass;
+        now->pre[tid] = sh.st.pre[tid]; now->rem[tid] = sh.st.rem[tid]; now->rep[tid] = sh.st.rep[tid];
+    }
+    const T* __restrict__ ex = a.ex + (size_t)b * a.cap;
+    const T* __restrict__ ey = a.ey + (size_t)b * a.cap;
+    const double mux = a.mu[2 * (size_t)b], muy = a.mu[2 * (size_t)b + 1];
+    const int64_t lo = (int64_t)span * a.span_chunks * kSpotChunk, end = lo + (int64_t)a.span_chunks * kSpotChunk, hi = n < end ? n : end;
+    const int shift = 56 - 8 * pass;
+    const unsigned long long himask = spot_himask(pass);
+    for (int64_t base = lo; base < hi; base += kSpotBlock) {
+        const int64_t i = base + tid;
+        unsigned long long key = 0ull;
+        if (i < hi) key = spot_key(ex[i], ey[i], mux, muy);
+        spot_bump(sh, nfrac, himask, shift, key, i < hi, lane);
+    }
+    __syncthreads();
+    unsigned* g = a.hist + ((size_t)b * kSpotPasses + pass) * hist_stride;
+    for (int e = tid; e < nfrac * 256; e += kSpotBlock) {
+        const unsigned v = sh.hist[e];
+        if (v) atomicAdd(g + e, v);
+    }
+}
+
 #undef ORT_ZF_FN
 
 }  // namespace ort

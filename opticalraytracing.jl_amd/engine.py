@@ -282,6 +282,33 @@ class HipEngine:
             otf = torch.view_as_complex(otf) if hasattr(otf, "data_ptr") else otf.view(np.complex128)[..., 0]
         return mtf, otf
 
+    # ---- GEO / encircled-energy radii of full_trace results ----
+    def spot_radii(self, ex, ey, count, fractions=(0.5, 0.8, 1.0)):
+        """`ort_spot_radii_f64` / `_f32` (by the dtype of ex): for nb full_trace slabs [nb][cap] with count[b] valid entries,
+        the centroid [nb][2] and, per fraction f, the radius about it that holds ceil(f count) of the entries [nb][nfrac] —
+        exact order statistics, f = 1 the GEO radius; both float64.  An empty bundle gives NaN.  `fractions` is a host
+        sequence of at most 8 values in (0, 1].  numpy arrays go through host buffers; torch CUDA tensors (ex, ey, count)
+        stay on the device — the call is asynchronous on the engine's stream and the results are torch tensors."""
+        nb, cap = ex.shape
+        frac = f64(fractions).ravel()
+        if hasattr(ex, "data_ptr"):
+            import torch
+            if ex.dtype not in (torch.float32, torch.float64) or ey.dtype != ex.dtype:
+                raise TypeError("spot_radii: ex, ey must both be float32 or both float64")
+            single = ex.dtype == torch.float32
+            centroid = torch.empty((nb, 2), dtype=torch.float64, device=ex.device)
+            radii = torch.empty((nb, frac.size), dtype=torch.float64, device=ex.device)
+            flags = self.base_flags | _capi.ORT_DEVICE_PTRS
+        else:
+            single = np.asarray(ex).dtype == np.float32
+            ex, ey = (np.ascontiguousarray(a, dtype=np.float32 if single else np.float64) for a in (ex, ey))
+            count = np.ascontiguousarray(count, dtype=np.int64)
+            centroid = np.empty((nb, 2)); radii = np.empty((nb, frac.size))
+            flags = self.base_flags
+        fn = self.ctx.lib.ort_spot_radii_f32 if single else self.ctx.lib.ort_spot_radii_f64
+        check(fn(self.ctx.h, int(nb), int(cap), ptr(count), ptr(ex), ptr(ey), int(frac.size), ptr(frac), ptr(centroid), ptr(radii), flags))
+        return centroid, radii
+
     # ---- meridional: raytrace(surfaces, y, U, RealRay)  RayTracing.jl:145-169 -----------
     def meridional(self, pres: Prescription, y, U, layout_mode: bool = False, isys: int = 0):
         y, U = (np.atleast_1d(f64(a)) for a in (y, U))
