@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64, ort_mtf_f64 and ort_spot_radii_f64 / _f32: new entry points only, nothing existing moved)
+#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64, ort_mtf_f64, ort_spot_radii_f64 / _f32, ort_geo_mtf_f64 / _f32 and ort_spot_image_f64 / _f32: new entry points only, nothing existing moved)
                                       0.4.1: ORT_FT_FUSED (full_trace's second pass inside the trace launch; bit-identical results) and its
                                       testing aid ort_ctx_test_fused_no_scan.  0.4.0: no new entry point; statistics-only full_trace walks tiles per workgroup (results within 1e-12 of
                                       0.3.0's); the device-side aiming loops trace without trigonometric calls only under ORT_FAST_MATH;
@@ -347,6 +347,44 @@ int ort_spot_radii_f32(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count,
                        const float *ex, const float *ey,
                        int nfrac, const double *frac /* [nfrac], HOST always */,
                        double *centroid /* [nb][2] or NULL */, double *radii /* [nb][nfrac] */, unsigned flags);
+/* Geometric MTF and spot density of nb full_trace results: the Fourier transform of the ray density along x and y, and
+ * the density itself on a pixel grid with its two line-spread functions, without bringing the vectors to the host (no
+ * reference counterpart: the reference's spot_diagram is a scatter plot).  Conventions common to both families:
+ *  - ex, ey : [nb][cap] with count[b] valid entries per slab, as for ort_spot_radii_*; entries at index count[b] and beyond
+ *    are never read (a count[b] > cap is read as cap).  The f32 variants promote each entry to binary64 on load; every sum
+ *    and every output is binary64 or integer.
+ *  - scale : [nb] or NULL (= 1); centre : [nb][2] or NULL (= 0).  Per entry gx = ex scale[b], dx = gx - centre[b][0] (one IEEE
+ *    product, one difference, in this order), the same for y.  scale = nu / lambda gives wavegrad units, in which the results
+ *    lie on ort_psf_f64's grid and ort_mtf_f64's axis; with scale NULL the centroid of ort_spot_radii_* can serve as centre.
+ *  - count, ex, ey, scale, centre and the outputs: host or device pointers per ORT_DEVICE_PTRS.  Inputs are assumed finite.
+ *  - ORT_EINVAL: NULL count, ex or ey, cap < 1 or cap >= 2^31, nb < 0, and the per-call ranges below.
+ * ort_geo_mtf_*: with nu_m = m dnu, m = 0 .. nfreq - 1, n = count[b]:  H_0(m) = (1 / n) sum_i exp(+i 2 pi nu_m dx_i), H_1 the
+ *    same with dy; otf[b][axis][m] = {Re H, Im H}, mtf = |H| — the layout and the sign of ort_mtf_f64: a spot wholly at
+ *    dx = xi0 gives exp(+i 2 pi nu xi0), what a tilt that moves the PSF peak to +xi0 gives there.  For a field along y axis 0
+ *    is sagittal, axis 1 tangential.  H(0) is exactly 1.  mtf is the plain-IEEE hypot of ort_mtf_f64 of exactly the two
+ *    numbers written to otf.  The sums are taken in one fixed order, without floating-point atomics: the same call gives the
+ *    same bits from run to run and with host or device pointers.  count[b] <= 0 gives NaN in that bundle's outputs; the call
+ *    still returns ORT_OK.  ORT_EINVAL: nfreq outside 1..512, dnu <= 0 or NaN, otf and mtf both NULL.
+ * ort_spot_image_*: ix = (int)floor(dx / dxi + 0.5) + nimg / 2 (one IEEE division, one addition), iy the same with dy: bin m
+ *    is centred on ort_psf_f64's sample centre + (m - nimg / 2) dxi.  image[b][iy][ix] counts the entries with both indices in
+ *    0 .. nimg - 1; lsf[b][0][ix] those with ix in range whatever iy, lsf[b][1][iy] likewise; outside[b] the entries not counted
+ *    in image.  Integer counting: exact, whatever the order of arrival; a host evaluating the same three operations per
+ *    coordinate gets the same integers.  count[b] <= 0 gives zeros.  ORT_EINVAL: nimg not a multiple of 16 in 16..128,
+ *    dxi <= 0 or NaN, image and lsf both NULL. */
+int ort_geo_mtf_f64(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count, const double *ex, const double *ey,
+                    const double *scale /* [nb] or NULL */, const double *centre /* [nb][2] or NULL */, int nfreq, double dnu,
+                    double *otf /* [nb][2][nfreq][2] or NULL */, double *mtf /* [nb][2][nfreq] or NULL */, unsigned flags);
+int ort_geo_mtf_f32(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count, const float *ex, const float *ey,
+                    const double *scale /* [nb] or NULL */, const double *centre /* [nb][2] or NULL */, int nfreq, double dnu,
+                    double *otf /* [nb][2][nfreq][2] or NULL */, double *mtf /* [nb][2][nfreq] or NULL */, unsigned flags);
+int ort_spot_image_f64(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count, const double *ex, const double *ey,
+                       const double *scale /* [nb] or NULL */, const double *centre /* [nb][2] or NULL */, int nimg, double dxi,
+                       int32_t *image /* [nb][nimg][nimg] or NULL */, int32_t *lsf /* [nb][2][nimg] or NULL */,
+                       int64_t *outside /* [nb] or NULL */, unsigned flags);
+int ort_spot_image_f32(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count, const float *ex, const float *ey,
+                       const double *scale /* [nb] or NULL */, const double *centre /* [nb][2] or NULL */, int nimg, double dxi,
+                       int32_t *image /* [nb][nimg][nimg] or NULL */, int32_t *lsf /* [nb][2][nimg] or NULL */,
+                       int64_t *outside /* [nb] or NULL */, unsigned flags);
 /* Testing aid: shift the context's look-back ticket base against the device counter, the bookkeeping fault that
  * ort_full_trace_* with ORT_FT_LOOKBACK must report (ORT_EHIP; device-pointer callers see count = -1, rms = NaN). */
 int ort_ctx_test_skew_tickets(ort_ctx *ctx, int64_t delta);

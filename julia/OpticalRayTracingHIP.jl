@@ -198,6 +198,55 @@ function spot_radii(ε, fractions::Vector{Float64} = [0.5, 0.8, 1.0])
     return c, r
 end
 
+"""
+    geo_mtf(ε::RealRayError; nfreq = 128, dnu = 2 / nfreq, λ = 587.5618e-6, centre = spot_radii(ε, [1.0])[1] .* (ε.nu / λ)) -> (freq, sagittal, tangential)
+
+Geometric MTF of a `full_trace` result of a field along y (`ort_geo_mtf_f64` / `_f32` by the element type): the modulus of the
+Fourier transform of the ray density along x and along y in `wavegrad` units, at `freq = dnu .* (0:nfreq-1)` — with the default
+`dnu` the axis of `mtf`.
+"""
+function geo_mtf(ε; nfreq::Integer = 128, dnu::Float64 = 2 / nfreq, λ::Float64 = 587.5618e-6,
+                 centre::Vector{Float64} = spot_radii(ε, [1.0])[1] .* (ε.nu / λ))
+    n = length(ε.x); cnt = Int64[n]; scale = Float64[ε.nu / λ]; out = Matrix{Float64}(undef, nfreq, 2)
+    if eltype(ε.x) === Float32
+        x = collect(Float32, ε.x); y = collect(Float32, ε.y)
+        GC.@preserve cnt x y scale centre out check(ccall((:ort_geo_mtf_f32, LIB), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}, Ptr{Float64}, Cint, Float64, Ptr{Float64}, Ptr{Float64}, UInt32),
+            ctx().h, 1, n, cnt, x, y, scale, centre, nfreq, dnu, C_NULL, out, 0))
+    else
+        x = collect(Float64, ε.x); y = collect(Float64, ε.y)
+        GC.@preserve cnt x y scale centre out check(ccall((:ort_geo_mtf_f64, LIB), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Float64, Ptr{Float64}, Ptr{Float64}, UInt32),
+            ctx().h, 1, n, cnt, x, y, scale, centre, nfreq, dnu, C_NULL, out, 0))
+    end
+    return dnu .* (0:nfreq-1), out[:, 1], out[:, 2]
+end
+
+"""
+    spot_image(ε::RealRayError; nimg = 64, dxi = 0.125, λ = 587.5618e-6, centre = ...) -> (image, lsf, outside)
+
+The spot as an image (`ort_spot_image_f64` / `_f32`): ray counts on an `nimg × nimg` grid of pitch `dxi` in `wavegrad` units whose
+bin `m` (0-based) is centred on `centre + (m - nimg ÷ 2) dxi`, the sample grid of `psf`; `image[ix+1, iy+1]` (column-major view of
+the C layout `[iy][ix]`), `lsf[:, 1]` / `lsf[:, 2]` the line-spread functions along x / y, `outside` the rays not in the image.
+"""
+function spot_image(ε; nimg::Integer = 64, dxi::Float64 = 0.125, λ::Float64 = 587.5618e-6,
+                    centre::Vector{Float64} = spot_radii(ε, [1.0])[1] .* (ε.nu / λ))
+    n = length(ε.x); cnt = Int64[n]; scale = Float64[ε.nu / λ]
+    image = Matrix{Int32}(undef, nimg, nimg); lsf = Matrix{Int32}(undef, nimg, 2); outside = Int64[0]
+    if eltype(ε.x) === Float32
+        x = collect(Float32, ε.x); y = collect(Float32, ε.y)
+        GC.@preserve cnt x y scale centre image lsf outside check(ccall((:ort_spot_image_f32, LIB), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}, Ptr{Float64}, Cint, Float64, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, UInt32),
+            ctx().h, 1, n, cnt, x, y, scale, centre, nimg, dxi, image, lsf, outside, 0))
+    else
+        x = collect(Float64, ε.x); y = collect(Float64, ε.y)
+        GC.@preserve cnt x y scale centre image lsf outside check(ccall((:ort_spot_image_f64, LIB), Cint,
+            (Ptr{Cvoid}, Cint, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Float64, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, UInt32),
+            ctx().h, 1, n, cnt, x, y, scale, centre, nimg, dxi, image, lsf, outside, 0))
+    end
+    return image, lsf, outside[1]
+end
+
 "Power-series coefficients of a row's polynomial; the closure handed to the CPU path is built from the same vector."
 poly(c::Vector{Float64}) = OpticalRayTracing.Polynomial(y -> evalpoly(y, c))
 

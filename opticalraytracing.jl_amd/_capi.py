@@ -133,6 +133,10 @@ SIGNATURES = {
     "ort_mtf_f64": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _u]),
     "ort_spot_radii_f64": (_i, [_p, _i, _l, _p, _p, _p, _i, _p, _p, _p, _u]),
     "ort_spot_radii_f32": (_i, [_p, _i, _l, _p, _p, _p, _i, _p, _p, _p, _u]),
+    "ort_geo_mtf_f64": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _i, C.c_double, _p, _p, _u]),
+    "ort_geo_mtf_f32": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _i, C.c_double, _p, _p, _u]),
+    "ort_spot_image_f64": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _i, C.c_double, _p, _p, _p, _u]),
+    "ort_spot_image_f32": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _i, C.c_double, _p, _p, _p, _u]),
     "ort_ctx_test_skew_tickets": (_i, [_p, _l]),
     "ort_ctx_test_fused_no_scan": (_i, [_p, _i]),
     "ort_aim_f64": (_i, [_p, _p, _p, _i, C.POINTER(ort_aim_in), C.POINTER(ort_aim_out), _u]),

@@ -903,6 +903,44 @@ def spot_radii(err: RealRayError, fractions=(0.5, 0.8, 1.0), engine=None):
     return c[0], r[0]
 
 
+def _geo_frame(err: RealRayError, lam, waves, centre, eng):
+    """(scale, centre) of `geo_mtf` / `spot_image`: waves = True scales the errors to wavegrad units (ε.nu / λ); centre = None
+    is the spot's centroid (`spot_radii`), brought to the same units by the same product."""
+    scale = err.nu / lam if waves else 1.0
+    if centre is None:
+        centre = eng.spot_radii(np.atleast_2d(err.x), np.atleast_2d(err.y), [len(err.x)], (1.0,))[0][0] * scale
+    return (np.array([scale]) if waves else None), np.atleast_2d(np.asarray(centre, dtype=np.float64))
+
+
+def geo_mtf(err: RealRayError, nfreq: int = 128, dnu=None, lam: float = LAMBDA, waves: bool = True, centre=None, engine=None):
+    """Geometric MTF of a full_trace result of a field along y, on the GPU (`ort_geo_mtf_f64` / `_f32`): (freq, mtf_sagittal,
+    mtf_tangential) — the modulus of the Fourier transform of the ray density along x and along y at freq = dnu (0 .. nfreq - 1),
+    the curve to trust when the wavefront error is many waves.  waves = True works in wavegrad units, where the default
+    dnu = 2 / nfreq gives `mtf_frequencies(nfreq)`, the axis of `mtf`, cut-off 2; waves = False in the prescription's length
+    unit (default dnu: the same frequencies times |ε.nu| / λ).  centre = None: about the centroid.  Device-resident slabs of
+    many bundles or the complex OTF: HipEngine.geo_mtf."""
+    eng = _eng(engine)
+    if dnu is None:
+        dnu = 2.0 / int(nfreq) * (1.0 if waves else abs(err.nu) / lam)
+    scale, centre = _geo_frame(err, lam, waves, centre, eng)
+    m, _ = eng.geo_mtf(np.atleast_2d(err.x), np.atleast_2d(err.y), [len(err.x)], nfreq, dnu, scale=scale, centre=centre)
+    return dnu * np.arange(int(nfreq)), m[0, 0], m[0, 1]
+
+
+def spot_image(err: RealRayError, nimg: int = 64, dxi=None, lam: float = LAMBDA, waves: bool = True, centre=None, engine=None):
+    """The spot of a full_trace result as an image, on the GPU (`ort_spot_image_f64` / `_f32`): (image [nimg][nimg] of ray
+    counts, indexed [iy][ix]; lsf [2][nimg], its line-spread functions along x and along y; the number of rays outside the
+    image).  Bin m is centred on centre + (m - nimg / 2) dxi, the sample grid of `psf` — waves = True in wavegrad units with the
+    default dxi = 0.125 of `psf`; waves = False in the prescription's length unit (default dxi: 0.125 λ / |ε.nu|).
+    centre = None: the centroid.  Device-resident slabs of many bundles: HipEngine.spot_image."""
+    eng = _eng(engine)
+    if dxi is None:
+        dxi = 0.125 * (1.0 if waves else lam / abs(err.nu))
+    scale, centre = _geo_frame(err, lam, waves, centre, eng)
+    image, lsf, outside = eng.spot_image(np.atleast_2d(err.x), np.atleast_2d(err.y), [len(err.x)], nimg, dxi, scale=scale, centre=centre)
+    return image[0], lsf[0], int(outside[0])
+
+
 # ---------------------------------------------------------------------------------------
 # transfer matrix (TransferMatrix.jl)
 # ---------------------------------------------------------------------------------------

@@ -82,7 +82,7 @@ enum { SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, S
        SL_TOFF, SL_TSQ, SL_AGG, SL_RES0, SL_RES1, SL_TAB0, SL_TAB1, SL_TAB2, SL_TAB3,
        SL_SB_FO, SL_SB_REC, SL_SB_MF, SL_SB_MR, SL_SB_TLF, SL_SB_TLR, SL_SB_AIN, SL_SB_AOUT, SL_SB_ENDS, SL_SB_FLAG,
        SL_SB_FIELDS, SL_SB_A, SL_SB_HP, SL_SB_PACK, SL_SB_CEXT, SL_SB_CREV, SL_FTSTATE, SL_FTTICKET, SL_FTERR, SL_FTDONE, SL_FTREADY, SL_DOMAIN, SL_RBSLOPES,
-       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_MTF_WS, SL_SPOT_WS, SL_COUNT };
+       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_MTF_WS, SL_SPOT_WS, SL_GEO_CENTRE, SL_GEO_WS, SL_COUNT };
 
 }  // namespace
 
@@ -1212,6 +1212,175 @@ int spot_radii_entry(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, co
     return ORT_OK;
 }
 
+// ---- geometric MTF and spot density (k_geo_mtf*, k_spot_image, ort_kernels.hpp) ----
+struct GeoPlan {
+    bool whole;              // one workgroup per bundle, results written by it
+    int nchunks;             // chunks of `chunk` entries per slab
+    int spans, span_chunks;  // otherwise: workgroups per bundle, chunks per workgroup
+};
+
+// The PSF's rule, by the slab size (the counts may lie on the device): from about four workgroups' worth of units per
+// compute unit on a workgroup walks a whole bundle; below, bundles are cut into spans of whole chunks.
+GeoPlan geo_plan(int nb, int64_t cap, int cus, int chunk, int units_per_bundle)
+{
+    GeoPlan pl;
+    pl.nchunks = (int)((cap + chunk - 1) / chunk);
+    pl.spans = 1; pl.span_chunks = pl.nchunks;
+    const int64_t target = 4 * (int64_t)std::max(cus, 1);
+    pl.whole = (int64_t)nb * units_per_bundle >= target;
+    if (!pl.whole) {
+        const int64_t spans = std::min<int64_t>(std::max<int64_t>((target + nb - 1) / nb, 1), pl.nchunks);
+        pl.span_chunks = (int)((pl.nchunks + spans - 1) / spans);
+        pl.spans = (pl.nchunks + pl.span_chunks - 1) / pl.span_chunks;
+    }
+    return pl;
+}
+
+template <typename T>
+GeoArgs<T> geo_args(const GeoPlan& pl, int64_t cap, const int64_t* count, const T* ex, const T* ey, const double* scale, const double* centre)
+{
+    GeoArgs<T> a;
+    memset(&a, 0, sizeof a);
+    a.nchunks = pl.nchunks; a.spans = pl.spans; a.span_chunks = pl.span_chunks; a.cap = cap;
+    a.count = count; a.ex = ex; a.ey = ey; a.scale = scale; a.centre = centre;
+    return a;
+}
+
+// every pointer is a device pointer; scale, centre and one of otf, mtf may be null
+template <typename T>
+int geo_mtf_device(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const T* ex, const T* ey, const double* scale,
+                   const double* centre, int nfreq, double dnu, double* otf, double* mtf)
+{
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const GeoPlan pl = geo_plan(nb, cap, cus, kGeoChunk, 2);
+    GeoArgs<T> a = geo_args<T>(pl, cap, count, ex, ey, scale, centre);
+    a.nfreq = nfreq; a.nblk = (nfreq + 15) / 16; a.dnu = dnu; a.otf = otf; a.mtf = mtf;
+    a.split = a.nblk == 1 ? 4 : a.nblk == 2 ? 2 : 1;            // fewer than 8 (axis, block) units: cut each over several waves
+    const dim3 block(kGeoBlock);
+    if (pl.whole) {
+        hipLaunchKernelGGL((k_geo_mtf<T>), dim3((unsigned)nb), block, 0, ctx->stream, a);
+        HIP_TRY(hipGetLastError());
+        return ORT_OK;
+    }
+    const size_t per_bundle = (size_t)pl.spans * 2 * a.nblk * 32;                // doubles
+    const int per_pass = (int)std::min<size_t>(std::max<size_t>(kZfWorkspaceBytes / (per_bundle * sizeof(double)), 1), (size_t)nb);
+    int rc = dev_out<double>(ctx, SL_GEO_WS, per_bundle * per_pass, &a.ws);
+    if (rc) return rc;
+    for (int b0 = 0; b0 < nb; b0 += per_pass) {                  // passes share the workspace: stream order keeps them apart
+        const int nbb = std::min(nb - b0, per_pass);
+        a.b0 = b0;
+        hipLaunchKernelGGL((k_geo_mtf_span<T>), dim3((unsigned)nbb * (unsigned)pl.spans), block, 0, ctx->stream, a);
+        hipLaunchKernelGGL(k_geo_mtf_fold, dim3((unsigned)nbb), block, 0, ctx->stream, b0, pl.spans, pl.span_chunks, nfreq, a.nblk, cap, count,
+                           (const double*)a.ws, otf, mtf);
+        HIP_TRY(hipGetLastError());
+    }
+    return ORT_OK;
+}
+
+// every pointer is a device pointer; scale, centre, outside and one of image, lsf may be null
+template <typename T>
+int spot_image_device(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const T* ex, const T* ey, const double* scale,
+                      const double* centre, int nimg, double dxi, int32_t* image, int32_t* lsf, int64_t* outside)
+{
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const GeoPlan pl = geo_plan(nb, cap, cus, kSpotChunk, 1);
+    GeoArgs<T> a = geo_args<T>(pl, cap, count, ex, ey, scale, centre);
+    a.nimg = nimg; a.dxi = dxi; a.image = image; a.lsf = lsf; a.outside = reinterpret_cast<unsigned long long*>(outside);
+    const size_t plane = (size_t)nimg * nimg, lds = ((image ? plane : 0) + 2 * (size_t)nimg + 1) * sizeof(unsigned);
+    const dim3 block(kGeoBlock);
+    if (pl.whole) {
+        if (lds > ((size_t)64 << 10))
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spot_image<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_spot_image<T, false>), dim3((unsigned)nb), block, lds, ctx->stream, a);
+    } else {
+        struct { void* p; size_t words; } out[3] = {{image, nb * plane}, {lsf, (size_t)nb * 2 * nimg}, {outside, (size_t)nb * 2}};
+        for (const auto& o : out)
+            if (o.p)
+                hipLaunchKernelGGL(k_spot_zero, dim3((unsigned)std::min<size_t>((o.words + kSpotBlock - 1) / kSpotBlock, 4096)), dim3(kSpotBlock), 0,
+                                   ctx->stream, static_cast<unsigned*>(o.p), o.words);
+        if (lds > ((size_t)64 << 10))
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spot_image<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_spot_image<T, true>), dim3((unsigned)nb * (unsigned)pl.spans), block, lds, ctx->stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return ORT_OK;
+}
+
+// what the two families share: the argument checks and the upload of a host caller's slabs
+template <typename T>
+struct GeoInputs { const int64_t* count; const T *ex, *ey; const double *scale, *centre; };
+
+int geo_check(const char* who, int nb, int64_t cap, const void* count, const void* ex, const void* ey)
+{
+    if (nb < 0 || cap < 1 || !count || !ex || !ey) return fail(ORT_EINVAL, "bad %s arguments", who);
+    if (cap > 0x7fffffffLL) return fail(ORT_EINVAL, "%s: cap %lld exceeds the 32-bit counters", who, (long long)cap);
+    return ORT_OK;
+}
+
+template <typename T>
+int geo_upload(ort_ctx* ctx, int nb, int64_t cap, GeoInputs<T>& in)
+{
+    const size_t n = (size_t)nb * (size_t)cap;
+    int rc = to_device<int64_t>(ctx, SL_IN0, in.count, (size_t)nb, &in.count); if (rc) return rc;
+    if (in.scale) { rc = to_device<double>(ctx, SL_IN1, in.scale, (size_t)nb, &in.scale); if (rc) return rc; }
+    rc = to_device<T>(ctx, SL_IN2, in.ex, n, &in.ex); if (rc) return rc;
+    rc = to_device<T>(ctx, SL_IN3, in.ey, n, &in.ey); if (rc) return rc;
+    if (in.centre) { rc = to_device<double>(ctx, SL_GEO_CENTRE, in.centre, (size_t)nb * 2, &in.centre); if (rc) return rc; }
+    return ORT_OK;
+}
+
+template <typename T>
+int geo_mtf_entry(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const T* ex, const T* ey, const double* scale, const double* centre,
+                  int nfreq, double dnu, double* otf, double* mtf, unsigned flags)
+{
+    int rc = check_ctx(ctx); if (rc) return rc;
+    rc = geo_check("geo_mtf", nb, cap, count, ex, ey); if (rc) return rc;
+    if (nfreq < 1 || nfreq > kGeoMaxFreq) return fail(ORT_EINVAL, "geo_mtf: nfreq %d outside 1..%d", nfreq, kGeoMaxFreq);
+    if (!(dnu > 0.0)) return fail(ORT_EINVAL, "geo_mtf: dnu %g is not positive", dnu);
+    if (!otf && !mtf) return fail(ORT_EINVAL, "geo_mtf: no output requested");
+    if (nb == 0) return ORT_OK;
+    if ((flags & ORT_DEVICE_PTRS)) return geo_mtf_device<T>(ctx, nb, cap, count, ex, ey, scale, centre, nfreq, dnu, otf, mtf);
+    GeoInputs<T> in{count, ex, ey, scale, centre};
+    rc = geo_upload<T>(ctx, nb, cap, in); if (rc) return rc;
+    const size_t curves = (size_t)nb * 2 * (size_t)nfreq;
+    double *dotf = nullptr, *dmtf = nullptr;
+    if (otf) { rc = dev_out<double>(ctx, SL_OUT0, 2 * curves, &dotf); if (rc) return rc; }
+    if (mtf) { rc = dev_out<double>(ctx, SL_OUT1, curves, &dmtf); if (rc) return rc; }
+    rc = geo_mtf_device<T>(ctx, nb, cap, in.count, in.ex, in.ey, in.scale, in.centre, nfreq, dnu, dotf, dmtf); if (rc) return rc;
+    if (otf) { rc = from_device<double>(ctx, otf, dotf, 2 * curves); if (rc) return rc; }
+    if (mtf) { rc = from_device<double>(ctx, mtf, dmtf, curves); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ORT_OK;
+}
+
+template <typename T>
+int spot_image_entry(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const T* ex, const T* ey, const double* scale, const double* centre,
+                     int nimg, double dxi, int32_t* image, int32_t* lsf, int64_t* outside, unsigned flags)
+{
+    int rc = check_ctx(ctx); if (rc) return rc;
+    rc = geo_check("spot_image", nb, cap, count, ex, ey); if (rc) return rc;
+    if (nimg < 16 || nimg > kGeoMaxImg || nimg % 16) return fail(ORT_EINVAL, "spot_image: nimg %d is not a multiple of 16 in 16..%d", nimg, kGeoMaxImg);
+    if (!(dxi > 0.0)) return fail(ORT_EINVAL, "spot_image: dxi %g is not positive", dxi);
+    if (!image && !lsf) return fail(ORT_EINVAL, "spot_image: no output requested");
+    if (nb == 0) return ORT_OK;
+    if ((flags & ORT_DEVICE_PTRS)) return spot_image_device<T>(ctx, nb, cap, count, ex, ey, scale, centre, nimg, dxi, image, lsf, outside);
+    GeoInputs<T> in{count, ex, ey, scale, centre};
+    rc = geo_upload<T>(ctx, nb, cap, in); if (rc) return rc;
+    const size_t n_img = (size_t)nb * nimg * nimg, n_lsf = (size_t)nb * 2 * nimg;
+    int32_t *dimg = nullptr, *dlsf = nullptr; int64_t* dout = nullptr;
+    if (image) { rc = dev_out<int32_t>(ctx, SL_OUT0, n_img, &dimg); if (rc) return rc; }
+    if (lsf) { rc = dev_out<int32_t>(ctx, SL_OUT1, n_lsf, &dlsf); if (rc) return rc; }
+    if (outside) { rc = dev_out<int64_t>(ctx, SL_OUT2, (size_t)nb, &dout); if (rc) return rc; }
+    rc = spot_image_device<T>(ctx, nb, cap, in.count, in.ex, in.ey, in.scale, in.centre, nimg, dxi, dimg, dlsf, dout); if (rc) return rc;
+    if (image) { rc = from_device<int32_t>(ctx, image, dimg, n_img); if (rc) return rc; }
+    if (lsf) { rc = from_device<int32_t>(ctx, lsf, dlsf, n_lsf); if (rc) return rc; }
+    if (outside) { rc = from_device<int64_t>(ctx, outside, dout, (size_t)nb); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ORT_OK;
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -1479,6 +1648,30 @@ int ort_spot_radii_f32(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, 
                        const double* frac, double* centroid, double* radii, unsigned flags)
 {
     return spot_radii_entry<float>(ctx, nb, cap, count, ex, ey, nfrac, frac, centroid, radii, flags);
+}
+
+int ort_geo_mtf_f64(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const double* ex, const double* ey, const double* scale,
+                    const double* centre, int nfreq, double dnu, double* otf, double* mtf, unsigned flags)
+{
+    return geo_mtf_entry<double>(ctx, nb, cap, count, ex, ey, scale, centre, nfreq, dnu, otf, mtf, flags);
+}
+
+int ort_geo_mtf_f32(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const float* ex, const float* ey, const double* scale,
+                    const double* centre, int nfreq, double dnu, double* otf, double* mtf, unsigned flags)
+{
+    return geo_mtf_entry<float>(ctx, nb, cap, count, ex, ey, scale, centre, nfreq, dnu, otf, mtf, flags);
+}
+
+int ort_spot_image_f64(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const double* ex, const double* ey, const double* scale,
+                       const double* centre, int nimg, double dxi, int32_t* image, int32_t* lsf, int64_t* outside, unsigned flags)
+{
+    return spot_image_entry<double>(ctx, nb, cap, count, ex, ey, scale, centre, nimg, dxi, image, lsf, outside, flags);
+}
+
+int ort_spot_image_f32(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, const float* ex, const float* ey, const double* scale,
+                       const double* centre, int nimg, double dxi, int32_t* image, int32_t* lsf, int64_t* outside, unsigned flags)
+{
+    return spot_image_entry<float>(ctx, nb, cap, count, ex, ey, scale, centre, nimg, dxi, image, lsf, outside, flags);
 }
 
 int ort_device_upload(ort_ctx* ctx, void* dst, const void* src, size_t bytes)

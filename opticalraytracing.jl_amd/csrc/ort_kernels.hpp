@@ -3681,6 +3681,262 @@ __global__ ORT_ZF_FN __launch_bounds__(kSpotBlock) void k_spot_select_span(SpotA
     }
 }
 
+
+// ------------------------------------------------------------------------------------
+// Geometric MTF and spot density of full_trace slabs on the device (ort_geo_mtf_f64 / _f32, ort_spot_image_f64 / _f32,
+// include/ort.h).  Both are sums over the entries of a slab, d = (ex scale - centre_x, ey scale - centre_y) per entry.
+//
+// Geometric MTF: H_axis(m) = (1 / n) sum_i exp(+i 2 pi m dnu d_i), a non-uniform DFT.  Nothing is reused between entries or
+// between frequencies, and FP64 MFMA has the FP64 VALU's peak on gfx950, so the sum is written for the VALU: a product form
+// (m = 16 a + b, a rank-16 matrix product per entry) would issue about five times the flops of the direct sum.
+//   A workgroup stages a chunk of kGeoChunk entries in LDS ONCE: d and the step exp(i 2 pi dnu d) of both axes.
+//   A unit is (axis, block of 16 frequencies); the 2 ceil(nfreq / 16) units are dealt to the 8 waves in turn.  With fewer
+//   than 8 units every unit is cut over `split` waves, which take the chunk's 64-entry rows in turn.
+//   A lane walks its entries in index order with 16 complex accumulators in registers: the block is seeded by sincospi of
+//   the directly formed phase (16 blk dnu) d — exactly (1, 0) in block 0, so that H(0) = n / n = 1 — and advanced by a
+//   complex rotation with the staged step: no recurrence runs longer than 15 steps.
+//   Order of the sums, fixed: lane (index order); the wave's 64 x 32 partial sums meet in an xor butterfly that halves the
+//   values a lane carries at every level (32 shuffles instead of 192; a + b on both sides of a pair: the same bits) and
+//   leaves value v on lanes 2 v, 2 v + 1; the chunk's sum is added to the unit's total in LDS (chunk order); the waves a
+//   unit was cut over are added in wave order; spans in span order.
+//   k_geo_mtf<T>       from 4 x CUs (bundle, axis) units on: one workgroup walks a whole bundle and writes its samples
+//   k_geo_mtf_span<T>  below: a bundle is cut into spans of whole chunks, the span's sums stored plainly to a workspace slot;
+//   k_geo_mtf_fold     adds them in span order.  No floating-point atomics anywhere.
+//
+// Spot density: ix = (int)floor(dx / dxi + 0.5) + nimg / 2 (one IEEE division, one addition), iy likewise; the image, its two
+// marginals (the line-spread functions) and the number of entries outside the image, all integers.
+//   k_spot_image<T, false>  from 4 x CUs bundles on: one workgroup per bundle counts into a histogram in dynamic LDS
+//                           (nimg^2 + 2 nimg + 1 counters, 65 KB at nimg = 128) with integer LDS atomics and stores it plainly;
+//   k_spot_image<T, true>   below: the outputs are zeroed (k_spot_zero), bundles are cut into spans of kSpotChunk entries and
+//                           a workgroup adds its non-zero counters to the outputs with integer global atomics.
+//   A wave whose entries all fall into one bin (a tight spot) adds their count with one atomic, as spot_bump does.
+// ------------------------------------------------------------------------------------
+constexpr int kGeoBlock = 512;
+constexpr int kGeoWaves = kGeoBlock / 64;
+constexpr int kGeoChunk = 1024;               // entries staged per step; the unit MTF spans are made of
+constexpr int kGeoMaxFreq = 512;
+constexpr int kGeoMaxUnits = 2 * kGeoMaxFreq / 16;        // (axis, block) pairs
+constexpr int kGeoMaxImg = 128;
+
+template <typename T>
+struct GeoArgs {
+    int nchunks, spans, span_chunks, b0;      // chunks per slab; workgroups per bundle, chunks per workgroup; first bundle of the pass
+    int64_t cap;
+    const int64_t* count;
+    const T *ex, *ey;
+    const double *scale, *centre;             // [nb] or null, [nb][2] or null
+    int nfreq, nblk, split;                   // MTF: samples, blocks of 16, waves per unit
+    double dnu;
+    double *otf, *mtf, *ws;                   // ws: [bundle of the pass][span][2 nblk][32]
+    int nimg;                                 // image
+    double dxi;
+    int *image, *lsf;
+    unsigned long long* outside;
+};
+
+struct GeoMtfShared {
+    double d[2][kGeoChunk], rc[2][kGeoChunk], rs[2][kGeoChunk];   // per axis: d, cos and sin of 2 pi dnu d
+    double tot[kGeoMaxUnits][32];                                 // per (unit, wave of the unit): 16 Re, 16 Im
+};
+
+// The 32 per-lane values of a wave summed over its lanes: value v is left in a[0] of lanes 2 v and 2 v + 1.
+template <int H>
+ORT_ZF_FN __device__ __forceinline__ void geo_wave_level(double (&a)[32], int lane)
+{
+    const bool up = (lane & (2 * H)) != 0;                       // the upper lane of a pair keeps the upper half of the values
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+        const double keep = up ? a[j + H] : a[j], send = up ? a[j] : a[j + H];
+        a[j] = keep + __shfl_xor(send, 2 * H);
+    }
+}
+ORT_ZF_FN __device__ __forceinline__ void geo_wave_sum(double (&a)[32], int lane)
+{
+    geo_wave_level<16>(a, lane); geo_wave_level<8>(a, lane); geo_wave_level<4>(a, lane); geo_wave_level<2>(a, lane);
+    geo_wave_level<1>(a, lane);
+    a[0] += __shfl_xor(a[0], 1);
+}
+
+// Chunks c0 .. c1 - 1 of bundle b (n > 0 entries) into sh.tot.  Called by whole workgroups.
+template <typename T>
+ORT_ZF_FN __device__ __forceinline__ void geo_mtf_walk(GeoMtfShared& sh, const GeoArgs<T>& a, int b, int64_t n, int c0, int c1, int tid)
+{
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), S = a.split, units = 2 * a.nblk * S;
+    const T* __restrict__ ex = a.ex + (size_t)b * a.cap;
+    const T* __restrict__ ey = a.ey + (size_t)b * a.cap;
+    const double sc = a.scale ? a.scale[b] : 1.0, cx = a.centre ? a.centre[2 * (size_t)b] : 0.0, cy = a.centre ? a.centre[2 * (size_t)b + 1] : 0.0;
+    for (int e = tid; e < units * 32; e += kGeoBlock) (&sh.tot[0][0])[e] = 0.0;
+    for (int c = c0; c < c1 && (int64_t)c * kGeoChunk < n; ++c) {
+        const int64_t lo = (int64_t)c * kGeoChunk;
+        const int m = (int)(n - lo < kGeoChunk ? n - lo : kGeoChunk);
+        __syncthreads();                                         // the previous chunk's readers are done; tot is zeroed
+        for (int e = tid; e < m; e += kGeoBlock) {
+            const double gx = (double)ex[lo + e] * sc, gy = (double)ey[lo + e] * sc, dx = gx - cx, dy = gy - cy;
+            double s, co;
+            sincospi(2.0 * (a.dnu * dx), &s, &co);
+            sh.d[0][e] = dx; sh.rc[0][e] = co; sh.rs[0][e] = s;
+            sincospi(2.0 * (a.dnu * dy), &s, &co);
+            sh.d[1][e] = dy; sh.rc[1][e] = co; sh.rs[1][e] = s;
+        }
+        __syncthreads();
+        for (int u = wave; u < units; u += kGeoWaves) {          // wave-uniform
+            const int item = u / S, sub = u - item * S, axis = item & 1, blk = item >> 1;
+            const double f0 = (double)(16 * blk) * a.dnu;
+            double acc[32];
+#pragma unroll
+            for (int j = 0; j < 32; ++j) acc[j] = 0.0;
+            for (int e = sub * 64 + lane; e < m; e += 64 * S) {
+                const double d = sh.d[axis][e], co = sh.rc[axis][e], s = sh.rs[axis][e];
+                double zr = 1.0, zi = 0.0;
+                if (blk) sincospi(2.0 * (f0 * d), &zi, &zr);
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    acc[j] += zr; acc[16 + j] += zi;
+                    if (j < 15) { const double t = zr * co - zi * s; zi = zr * s + zi * co; zr = t; }
+                }
+            }
+            geo_wave_sum(acc, lane);
+            if (!(lane & 1)) sh.tot[u][lane >> 1] += acc[0];     // the same lane of the same wave in every chunk
+        }
+    }
+    __syncthreads();
+}
+
+// A unit's value v (Re of sample j: v = j; Im: v = 16 + j), the waves it was cut over added in wave order
+ORT_ZF_FN __device__ __forceinline__ double geo_unit_sum(const GeoMtfShared& sh, int item, int v, int S)
+{
+    double t = 0.0;
+    for (int s = 0; s < S; ++s) t += sh.tot[item * S + s][v];
+    return t;
+}
+
+// sample m of (bundle b, axis) from its sums
+ORT_ZF_FN __device__ __forceinline__ void geo_mtf_store(double* otf, double* mtf, int b, int axis, int m, int nfreq, double re, double im, int64_t n)
+{
+    const double nan = __builtin_nan("");
+    re = n > 0 ? re / (double)n : nan; im = n > 0 ? im / (double)n : nan;
+    const size_t o = ((size_t)b * 2 + axis) * nfreq + m;
+    if (otf) { otf[2 * o] = re; otf[2 * o + 1] = im; }
+    if (mtf) mtf[o] = n > 0 ? mtf_hypot(re, im) : nan;
+}
+
+// Grid: bundles.
+template <typename T>
+__global__ ORT_ZF_FN __launch_bounds__(kGeoBlock) void k_geo_mtf(GeoArgs<T> a)
+{
+    __shared__ GeoMtfShared sh;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int64_t n = spot_entries(a.count, b, a.cap);
+    if (n > 0) geo_mtf_walk(sh, a, b, n, 0, a.nchunks, tid);     // uniform
+    for (int o = tid; o < 2 * a.nfreq; o += kGeoBlock) {
+        const int axis = o / a.nfreq, m = o - axis * a.nfreq, item = 2 * (m >> 4) + axis, j = m & 15;
+        double re = 0.0, im = 0.0;
+        if (n > 0) { re = geo_unit_sum(sh, item, j, a.split); im = geo_unit_sum(sh, item, 16 + j, a.split); }
+        geo_mtf_store(a.otf, a.mtf, b, axis, m, a.nfreq, re, im, n);
+    }
+}
+
+// Grid: bundles of the pass x spans.  A span that starts at or beyond count[b] stores nothing; the fold does not read its slot.
+template <typename T>
+__global__ ORT_ZF_FN __launch_bounds__(kGeoBlock) void k_geo_mtf_span(GeoArgs<T> a)
+{
+    __shared__ GeoMtfShared sh;
+    const int tid = threadIdx.x, bl = blockIdx.x / a.spans, span = blockIdx.x - bl * a.spans, b = a.b0 + bl;
+    const int64_t n = spot_entries(a.count, b, a.cap);
+    const int c0 = span * a.span_chunks, c1 = min(c0 + a.span_chunks, a.nchunks);
+    if ((int64_t)c0 * kGeoChunk >= n) return;                    // uniform
+    geo_mtf_walk(sh, a, b, n, c0, c1, tid);
+    double* slot = a.ws + (size_t)blockIdx.x * (2 * a.nblk * 32);
+    for (int e = tid; e < 2 * a.nblk * 32; e += kGeoBlock) slot[e] = geo_unit_sum(sh, e >> 5, e & 31, a.split);
+}
+
+// Grid: bundles of the pass.  The spans' sums in span order.
+__global__ ORT_ZF_FN __launch_bounds__(kGeoBlock) void k_geo_mtf_fold(int b0, int spans, int span_chunks, int nfreq, int nblk, int64_t cap,
+                                                                      const int64_t* __restrict__ count, const double* __restrict__ ws,
+                                                                      double* __restrict__ otf, double* __restrict__ mtf)
+{
+    const int b = b0 + blockIdx.x;
+    const int64_t n = spot_entries(count, b, cap);
+    const size_t stride = (size_t)2 * nblk * 32;
+    const double* part = ws + (size_t)blockIdx.x * spans * stride;
+    for (int o = threadIdx.x; o < 2 * nfreq; o += kGeoBlock) {
+        const int axis = o / nfreq, m = o - axis * nfreq, item = 2 * (m >> 4) + axis, j = m & 15;
+        double re = 0.0, im = 0.0;
+        for (int s = 0; s < spans && (int64_t)s * span_chunks * kGeoChunk < n; ++s) {
+            re += part[s * stride + item * 32 + j]; im += part[s * stride + item * 32 + 16 + j];
+        }
+        geo_mtf_store(otf, mtf, b, axis, m, nfreq, re, im, n);
+    }
+}
+
+// Bin index 0 .. nimg - 1 of a coordinate, or -1 outside the image
+ORT_ZF_FN __device__ __forceinline__ int geo_bin(double d, double dxi, int nimg)
+{
+    const double t = floor(d / dxi + 0.5);
+    const int half = nimg / 2;
+    return t >= (double)-half && t < (double)(nimg - half) ? (int)t + half : -1;
+}
+
+// One count per lane with m set into hist[idx].  Called by whole waves.
+ORT_ZF_FN __device__ __forceinline__ void geo_count(unsigned* hist, int idx, bool m, int lane)
+{
+    const unsigned long long bal = __ballot(m);
+    if (bal == 0ull) return;
+    const int leader = __ffsll((long long)bal) - 1;
+    const int il = __shfl(idx, leader);
+    if (__all(!m || idx == il)) { if (lane == leader) atomicAdd(&hist[il], (unsigned)__popcll(bal)); }
+    else if (m) atomicAdd(&hist[idx], 1u);
+}
+
+extern __shared__ unsigned geo_img_lds[];
+
+// Grid: bundles (SPAN = false) or bundles x spans.  Dynamic LDS: (image ? nimg^2 : 0) + 2 nimg + 1 counters.
+template <typename T, bool SPAN>
+__global__ ORT_ZF_FN __launch_bounds__(kGeoBlock) void k_spot_image(GeoArgs<T> a)
+{
+    const int tid = threadIdx.x, lane = tid & 63, nimg = a.nimg, nim = a.image ? nimg * nimg : 0, words = nim + 2 * nimg + 1;
+    const int b = SPAN ? blockIdx.x / a.spans : blockIdx.x, span = SPAN ? blockIdx.x - b * a.spans : 0;
+    unsigned *img = geo_img_lds, *ls = img + nim, *outc = ls + 2 * nimg;
+    const int64_t n = spot_entries(a.count, b, a.cap);
+    int64_t lo = 0, hi = n > 0 ? n : 0;
+    if (SPAN) {
+        lo = (int64_t)span * a.span_chunks * kSpotChunk;
+        const int64_t end = lo + (int64_t)a.span_chunks * kSpotChunk;
+        hi = hi < end ? hi : end;
+        if (lo >= hi) return;                                    // uniform; the outputs are zeroed already
+    }
+    for (int e = tid; e < words; e += kGeoBlock) img[e] = 0u;
+    __syncthreads();
+    const T* __restrict__ ex = a.ex + (size_t)b * a.cap;
+    const T* __restrict__ ey = a.ey + (size_t)b * a.cap;
+    const double sc = a.scale ? a.scale[b] : 1.0, cx = a.centre ? a.centre[2 * (size_t)b] : 0.0, cy = a.centre ? a.centre[2 * (size_t)b + 1] : 0.0;
+    unsigned nout = 0u;                                          // wave-uniform
+    for (int64_t base = lo; base < hi; base += kGeoBlock) {
+        const int64_t i = base + tid;
+        int ix = -1, iy = -1;
+        if (i < hi) {
+            const double gx = (double)ex[i] * sc, gy = (double)ey[i] * sc;
+            ix = geo_bin(gx - cx, a.dxi, nimg); iy = geo_bin(gy - cy, a.dxi, nimg);
+        }
+        const bool in = ix >= 0 && iy >= 0;
+        if (a.image) geo_count(img, iy * nimg + ix, in, lane);
+        if (a.lsf) { geo_count(ls, ix, ix >= 0, lane); geo_count(ls + nimg, iy, iy >= 0, lane); }
+        nout += (unsigned)__popcll(__ballot(i < hi && !in));
+    }
+    if (lane == 0 && nout) atomicAdd(outc, nout);
+    __syncthreads();
+    int* image = a.image + (size_t)b * nim;                      // (unused when null: nim = 0)
+    if (SPAN) {
+        for (int e = tid; e < nim; e += kGeoBlock) { const unsigned v = img[e]; if (v) atomicAdd(image + e, (int)v); }
+        if (a.lsf) for (int e = tid; e < 2 * nimg; e += kGeoBlock) { const unsigned v = ls[e]; if (v) atomicAdd(a.lsf + (size_t)b * 2 * nimg + e, (int)v); }
+        if (tid == 0 && a.outside && *outc) atomicAdd(a.outside + b, (unsigned long long)*outc);
+    } else {
+        for (int e = tid; e < nim; e += kGeoBlock) image[e] = (int)img[e];
+        if (a.lsf) for (int e = tid; e < 2 * nimg; e += kGeoBlock) a.lsf[(size_t)b * 2 * nimg + e] = (int)ls[e];
+        if (tid == 0 && a.outside) a.outside[b] = *outc;
+    }
+}
+
 #undef ORT_ZF_FN
 
 }  // namespace ort

@@ -309,6 +309,66 @@ class HipEngine:
         check(fn(self.ctx.h, int(nb), int(cap), ptr(count), ptr(ex), ptr(ey), int(frac.size), ptr(frac), ptr(centroid), ptr(radii), flags))
         return centroid, radii
 
+    # ---- geometric MTF and spot density of full_trace results ----
+    def _geo_inputs(self, who, ex, ey, count, scale, centre):
+        """What `geo_mtf` and `spot_image` share: (on_device, single, ex, ey, count, scale, centre, flags).  numpy inputs are made
+        contiguous in their dtype; torch CUDA tensors are taken as they are (scale, centre: float64 tensors or None)."""
+        if hasattr(ex, "data_ptr"):
+            import torch
+            if ex.dtype not in (torch.float32, torch.float64) or ey.dtype != ex.dtype:
+                raise TypeError(f"{who}: ex, ey must both be float32 or both float64")
+            return True, ex.dtype == torch.float32, ex, ey, count, scale, centre, self.base_flags | _capi.ORT_DEVICE_PTRS
+        single = np.asarray(ex).dtype == np.float32
+        ex, ey = (np.ascontiguousarray(a, dtype=np.float32 if single else np.float64) for a in (ex, ey))
+        nb = ex.shape[0]
+        scale = None if scale is None else np.ascontiguousarray(np.broadcast_to(f64(scale), (nb,)))
+        centre = None if centre is None else np.ascontiguousarray(np.broadcast_to(f64(centre), (nb, 2)))
+        return False, single, ex, ey, np.ascontiguousarray(count, dtype=np.int64), scale, centre, self.base_flags
+
+    def geo_mtf(self, ex, ey, count, nfreq: int, dnu: float, scale=None, centre=None, want_otf: bool = False):
+        """`ort_geo_mtf_f64` / `_f32` (by the dtype of ex): the geometric MTF [nb][2][nfreq] of nb full_trace slabs [nb][cap]
+        with count[b] valid entries — the modulus of the mean of exp(+i 2 pi m dnu d) over the entries, d = ex scale - centre_x
+        (axis 0) or ey scale - centre_y (axis 1), m = 0 .. nfreq - 1.  scale [nb] (None: 1; nu / lambda gives wavegrad units, the
+        axis of `mtf`) and centre [nb][2] (None: 0).  Returns (mtf, otf or None), shaped as `mtf`; an empty bundle gives NaN.
+        numpy arrays go through host buffers; torch CUDA tensors (ex, ey, count, and scale / centre when given) stay on the
+        device — the call is asynchronous on the engine's stream and the results are torch tensors."""
+        on_dev, single, ex, ey, count, scale, centre, flags = self._geo_inputs("geo_mtf", ex, ey, count, scale, centre)
+        nb, cap = ex.shape
+        if on_dev:
+            import torch
+            otf = torch.empty((nb, 2, nfreq, 2), dtype=torch.float64, device=ex.device) if want_otf else None
+            mtf = torch.empty((nb, 2, nfreq), dtype=torch.float64, device=ex.device)
+        else:
+            otf = np.empty((nb, 2, nfreq, 2)) if want_otf else None
+            mtf = np.empty((nb, 2, nfreq))
+        fn = self.ctx.lib.ort_geo_mtf_f32 if single else self.ctx.lib.ort_geo_mtf_f64
+        check(fn(self.ctx.h, int(nb), int(cap), ptr(count), ptr(ex), ptr(ey), ptr(scale), ptr(centre), int(nfreq), float(dnu),
+                 ptr(otf), ptr(mtf), flags))
+        if otf is not None:
+            otf = torch.view_as_complex(otf) if on_dev else otf.view(np.complex128)[..., 0]
+        return mtf, otf
+
+    def spot_image(self, ex, ey, count, nimg: int, dxi: float, scale=None, centre=None):
+        """`ort_spot_image_f64` / `_f32` (by the dtype of ex): the spot density of nb full_trace slabs on an nimg x nimg pixel grid
+        of pitch dxi whose bin m is centred on centre + (m - nimg / 2) dxi, the sample grid of `psf`: (image [nb][nimg][nimg]
+        int32, indexed [iy][ix]; lsf [nb][2][nimg] int32, the marginals along x and along y, which also count entries outside the
+        image in the other direction; outside [nb] int64, the entries not in image).  Exact integer counts.  scale, centre and
+        the numpy / torch conventions: as `geo_mtf`."""
+        on_dev, single, ex, ey, count, scale, centre, flags = self._geo_inputs("spot_image", ex, ey, count, scale, centre)
+        nb, cap = ex.shape
+        if on_dev:
+            import torch
+            image = torch.empty((nb, nimg, nimg), dtype=torch.int32, device=ex.device)
+            lsf = torch.empty((nb, 2, nimg), dtype=torch.int32, device=ex.device)
+            outside = torch.empty(nb, dtype=torch.int64, device=ex.device)
+        else:
+            image = np.empty((nb, nimg, nimg), dtype=np.int32); lsf = np.empty((nb, 2, nimg), dtype=np.int32)
+            outside = np.empty(nb, dtype=np.int64)
+        fn = self.ctx.lib.ort_spot_image_f32 if single else self.ctx.lib.ort_spot_image_f64
+        check(fn(self.ctx.h, int(nb), int(cap), ptr(count), ptr(ex), ptr(ey), ptr(scale), ptr(centre), int(nimg), float(dxi),
+                 ptr(image), ptr(lsf), ptr(outside), flags))
+        return image, lsf, outside
+
     # ---- meridional: raytrace(surfaces, y, U, RealRay)  RayTracing.jl:145-169 -----------
     def meridional(self, pres: Prescription, y, U, layout_mode: bool = False, isys: int = 0):
         y, U = (np.atleast_1d(f64(a)) for a in (y, U))
