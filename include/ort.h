@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64, ort_mtf_f64, ort_spot_radii_f64 / _f32, ort_geo_mtf_f64 / _f32 and ort_spot_image_f64 / _f32: new entry points only, nothing existing moved)
+#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64, ort_mtf_f64, ort_spot_radii_f64 / _f32, ort_geo_mtf_f64 / _f32, ort_spot_image_f64 / _f32 and ort_opd_grid_f64: new entry points only, nothing existing moved)
                                       0.4.1: ORT_FT_FUSED (full_trace's second pass inside the trace launch; bit-identical results) and its
                                       testing aid ort_ctx_test_fused_no_scan.  0.4.0: no new entry point; statistics-only full_trace walks tiles per workgroup (results within 1e-12 of
                                       0.3.0's); the device-side aiming loops trace without trigonometric calls only under ORT_FAST_MATH;
@@ -385,6 +385,50 @@ int ort_spot_image_f32(ort_ctx *ctx, int nb, int64_t cap, const int64_t *count, 
                        const double *scale /* [nb] or NULL */, const double *centre /* [nb][2] or NULL */, int nimg, double dxi,
                        int32_t *image /* [nb][nimg][nimg] or NULL */, int32_t *lsf /* [nb][2][nimg] or NULL */,
                        int64_t *outside /* [nb] or NULL */, unsigned flags);
+/* Wavefront OPD by optical path length: the optical path difference of every ray of nb pupil-grid bundles against a reference
+ * sphere, in waves, with its statistics — the primary quantity the fit / PSF / MTF chain above infers from transverse errors,
+ * here free of any polynomial truncation (no reference counterpart: the reference stops at wavegrad and the fit).
+ *  - bundles, axes, the ray numbering and status: exactly those of ort_trace_grid_f64; the last row of the prescription is the
+ *    image plane, as full_trace appends it.  Positions are traced with the reference sequence (the default policy's step
+ *    functions): x, y and status are bit-identical to ort_trace_grid_f64 without ORT_FAST_MATH.  ORT_FAST_MATH is accepted and
+ *    ignored, as it is for deep prescriptions.  Float64 only: 1e-3 waves sit eleven digits below the track length.
+ *  - optical path of a ray.  g_i = (v_i, u_i, 1) is its slope vector in space i (before the step to row i+1), h_i = |g_i|,
+ *    s_i the sag the trace applied at row i+1 (s_-1 = 0), dz_i = t_i - s_(i-1) + s_i.  Segment length d_i = dz_i h_i, signed: in
+ *    a mirror space n, t and dz are negative and n_i d_i > 0.  Launch term, the plane wavefront through the origin of the launch
+ *    plane: n_0 (k0 x_L + k1 y_L), k = g_0 / h_0.  Last leg, from the image-plane hit Q = (xf, yf) along the arriving slope
+ *    vector g' to the sphere: w = (xf - px, yf - py, 0), disc = (w.g')^2 - h'^2 (|w|^2 - radius^2),
+ *    tau = (-(w.g') - sign(radius) sqrt(disc)) / h'^2, the root on the exit-pupil side.
+ *        E = n_0 (k0 x_L + k1 y_L) + sum_i n_i (d_i - t_i) + n' (tau h' + radius)
+ *    The constants sum n_i t_i and n' radius, common to every ray of a bundle, are dropped, and both excesses are formed without
+ *    cancellation: d_i - t_i = (s_i - s_(i-1)) h_i + t_i q_i / (1 + h_i), q_i = u_i^2 + v_i^2; tau h' + radius likewise.
+ *  - W = (E_ref - E_ray) / lambda.  Sign: that of wavegrad — dW/drho = eps . nu / lambda; an ideal spherical wave defocused
+ *    by focus - F over a pupil of semi-diameter a gives W = -(a^2 / 2F)(1 - focus / F) rho^2 to paraxial accuracy.
+ *  - reference ray: launched at (y0, x0) with the bundle's U, V through the same step functions.  px or py NaN: its own image
+ *    hit is the centre of the sphere (chief-ray-referenced OPD, tilt removed).  If it misses, is stopped, is vignetted or has
+ *    disc < 0, the bundle has no OPD: count[b] = -1, mean, rms, pv and all of opd[b] are NaN; the call still returns ORT_OK.
+ *  - a ray contributes to opd and to the statistics exactly when full_trace would keep it (not ORT_STATUS_STOPPED, not
+ *    ORT_STATUS_VIGNETTED, xf and yf not NaN) and disc >= 0; every other node of opd is NaN.
+ *  - count[b] = contributing rays; mean[b] = mean of W; rms[b] = its RMS about that mean; pv[b] = max - min.  count[b] = 0 gives
+ *    NaN statistics.  (n, mean, M2, min, max) partials of tiles of 256 rays are merged in tile order in one fixed tree, without
+ *    floating-point atomics: the same call gives the same bits from run to run and with host or device pointers, and a
+ *    bundle's numbers depend on the bundle alone.
+ *  - NOT BUILT: ORT_RAYBASIS.  The reference forms those rays' angles as (ybar - y) / z0 and takes tan of them, so they do not
+ *    leave one object point and no launch wavefront is defined.
+ * refs : [nb], HOST always (like bundles); opd : [nb][ny][nx] or NULL; status : [nb ny nx] or NULL; count, rms : [nb];
+ * mean, pv : [nb] or NULL.  axes and the outputs: host or device pointers per ORT_DEVICE_PTRS.
+ * ORT_EINVAL: a NULL among sys, bundles, refs, axes, count, rms; lambda <= 0 or NaN; a radius zero or not finite; a bundle with
+ * stop == 0; ORT_RAYBASIS; the shape errors of ort_trace_grid_f64. */
+typedef struct ort_opd_ref {
+    double y0, x0;     /* launch coordinates of the bundle's reference ray, on the plane of the pupil axes */
+    double px, py;     /* centre of the reference sphere in the image plane; NaN, NaN = the reference ray's own hit */
+    double radius;     /* signed: z_image - z_exit_pupil (> 0 when the exit pupil lies before the image); finite, non-zero */
+} ort_opd_ref;
+int ort_opd_grid_f64(ort_ctx *ctx, const ort_system *sys, int nb, const ort_bundle *bundles,
+                     const ort_opd_ref *refs /* [nb], HOST always, like bundles */,
+                     const double *axes, int64_t axes_len, int ny, int nx, double lambda,
+                     double *opd /* [nb][ny][nx] waves, or NULL */, int32_t *status /* [N] or NULL */,
+                     int64_t *count /* [nb] */, double *mean, double *rms, double *pv /* [nb] each; mean/pv may be NULL */,
+                     unsigned flags);
 /* Testing aid: shift the context's look-back ticket base against the device counter, the bookkeeping fault that
  * ort_full_trace_* with ORT_FT_LOOKBACK must report (ORT_EHIP; device-pointer callers see count = -1, rms = NaN). */
 int ort_ctx_test_skew_tickets(ort_ctx *ctx, int64_t delta);

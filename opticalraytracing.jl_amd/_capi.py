@@ -55,6 +55,10 @@ class ort_bundle(C.Structure):
     ]
 
 
+class ort_opd_ref(C.Structure):
+    _fields_ = [("y0", C.c_double), ("x0", C.c_double), ("px", C.c_double), ("py", C.c_double), ("radius", C.c_double)]
+
+
 class ort_aim_in(C.Structure):
     _fields_ = [
         ("system", C.c_int32), ("stop", C.c_int32), ("layout_fwd", C.c_int32), ("layout_rev", C.c_int32),
@@ -137,6 +141,8 @@ SIGNATURES = {
     "ort_geo_mtf_f32": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _i, C.c_double, _p, _p, _u]),
     "ort_spot_image_f64": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _i, C.c_double, _p, _p, _p, _u]),
     "ort_spot_image_f32": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _i, C.c_double, _p, _p, _p, _u]),
+    "ort_opd_grid_f64": (_i, [_p, _p, _i, C.POINTER(ort_bundle), C.POINTER(ort_opd_ref), _p, _l, _i, _i, C.c_double,
+                              _p, _p, _p, _p, _p, _p, _u]),
     "ort_ctx_test_skew_tickets": (_i, [_p, _l]),
     "ort_ctx_test_fused_no_scan": (_i, [_p, _i]),
     "ort_aim_f64": (_i, [_p, _p, _p, _i, C.POINTER(ort_aim_in), C.POINTER(ort_aim_out), _u]),

@@ -941,6 +941,40 @@ def spot_image(err: RealRayError, nimg: int = 64, dxi=None, lam: float = LAMBDA,
     return image[0], lsf[0], int(outside[0])
 
 
+@dataclass
+class WavefrontOPD:
+    """`opd`: the wavefront of one field on the half pupil full_trace samples, by optical path length."""
+    opd: np.ndarray        # [k_rays][k_rays // 2] waves; NaN where the ray does not reach the image
+    y: np.ndarray          # launch coordinates of the rows ...
+    x: np.ndarray          # ... and of the columns (the x >= 0 half: the pupil is symmetric about the meridional plane)
+    count: int             # contributing rays; -1: the reference ray did not get through
+    mean: float
+    rms: float             # about the mean
+    pv: float
+
+
+def opd(system: System, H: float, k_rays: int = SPOT_RAYS, lam: float = LAMBDA, focus=None, engine=None) -> WavefrontOPD:
+    """Optical path difference of the rays of `full_trace(system, H, k_rays, focus)` against the reference sphere centred on the
+    chief ray's image point, in waves of `lam`, on the GPU (`ort_opd_grid_f64`): the wavefront itself — RMS and peak-to-valley
+    free of any polynomial truncation — where `zernike_fit` infers it from the transverse errors.  Aiming and prescription are
+    those of `full_trace_aim` / `full_trace_grid`; the reference ray is launched midway between the two edge rays, and the
+    sphere's radius is focus - XP_t with XP_t the real chief ray's exit-pupil distance from the last vertex.  Many bundles or
+    device-resident outputs: HipEngine.opd_grid."""
+    eng = _eng(engine)
+    surfaces = system.layout
+    aim = full_trace_aim(surfaces, system, H, focus, engine=eng)
+    if aim.raybasis:
+        raise ValueError("opd: finite-conjugate (RayBasis) bundles have no launch wavefront; not built")
+    real_chief = trace_chief_ray(surfaces, system, engine=eng)
+    XP_t = real_chief.z[-1] - real_chief.z[-2]
+    k_rays, k2 = int(k_rays), int(k_rays) // 2
+    yax, xax = linrange(aim.y1, aim.y2, k_rays), linrange(0.0, aim.y_EP, k2)
+    bundle = dict(system=0, stop=aim.stop, U=aim.U, V=aim.V, a_stop=aim.a_stop, hprime=aim.hprime, yaxis_off=0, xaxis_off=k_rays)
+    ref = dict(y0=0.5 * (aim.y1 + aim.y2), x0=0.0, radius=aim.focus - XP_t)
+    r = eng.opd_grid(extended_prescription(surfaces, aim.focus), [bundle], [ref], np.concatenate([yax, xax]), k_rays, k2, lam)[0]
+    return WavefrontOPD(r["opd"], yax, xax, int(r["count"]), float(r["mean"]), float(r["rms"]), float(r["pv"]))
+
+
 # ---------------------------------------------------------------------------------------
 # transfer matrix (TransferMatrix.jl)
 # ---------------------------------------------------------------------------------------

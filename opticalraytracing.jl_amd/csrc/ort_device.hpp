@@ -491,6 +491,40 @@ __device__ __forceinline__ void surface_step_ieee_flat(Ray<T>& r, const SurfRec<
     ieee_div2(r.k1, r.k0, r.k2, r.u, r.v);           // :59-60
 }
 
+// ---- optical path along the reference sequence (ort_opd_grid_f64) ---------------------------------------------
+// One iteration moves a ray from its point on row i to its point on row i+1 along the slope vector g = (v, u, 1) it had
+// BEFORE the step, over dz = t - s_prev + s: a segment of signed length d = dz h, h = |g| = sqrt(1 + q), q = u^2 + v^2.
+// The vertex spacing t is common to every ray of a system and cancels from every optical path DIFFERENCE, so only the excess
+//     d - t = (s - s_prev) h + t (h - 1),        h - 1 = q / (1 + h)   (no cancellation for a ray near the axis)
+// is kept: millimetres where the track is hundreds, which is what leaves 1e-3 waves eleven digits below the track length
+// resolvable in binary64.  ds = s - s_prev as the step left it (Ray::sprev after minus before).
+__device__ __forceinline__ double opd_segment_excess(double t, double ds, double u, double v)
+{
+    const double q = u * u + v * v;
+    const double h = ieee_sqrt(1.0 + q);
+    return ds * h + ieee_div(t * q, 1.0 + h);
+}
+
+// The last leg: from the image-plane hit Q back (or on) along the arriving slope vector g' = (v, u, 1) to the reference
+// sphere of signed radius `radius` about C in the image plane; w = Q - C = (wx, wy, 0).  The point Q + tau g' lies on the
+// sphere for  tau = (-(w.g') - sign(radius) sqrt(disc)) / h'^2,  disc = (w.g')^2 - h'^2 (|w|^2 - radius^2)  — the root on
+// the exit-pupil side; the leg's signed length is tau h' = -radius + O(|w|).  The constant -radius is common to every ray of a
+// bundle (the reference ray included) and is dropped like t above; what is returned is
+//     leg = tau h' + radius = (-(w.g') + sign(radius) (h'^2 |w|^2 - (w.g')^2) / (|radius| h' + sqrt(disc))) / h'
+// (|radius| h' - sqrt(disc) rationalised; h'^2 |w|^2 - (w.g')^2 >= 0 by Cauchy-Schwarz): every term is of the size of the spot.
+// Returns disc >= 0 (false for NaN): whether the ray meets the sphere at all.
+__device__ __forceinline__ bool opd_sphere_leg(double wx, double wy, double u, double v, double radius, double& leg)
+{
+    const double h2 = 1.0 + (u * u + v * v), h = ieee_sqrt(h2);
+    const double wg = wx * v + wy * u, ww = wx * wx + wy * wy;
+    const double disc = wg * wg - h2 * (ww - radius * radius);
+    const double sq = ieee_sqrt(disc);                                  // NaN for disc < 0
+    const double num = h2 * ww - wg * wg, den = t_abs(radius) * h + sq;
+    const double corr = ieee_div(num, den);
+    leg = ieee_div(radius > 0.0 ? corr - wg : -corr - wg, h);
+    return disc >= 0.0;
+}
+
 // |a| < lim as ONE compare (source modifier); false for NaN: a ray that missed outright is no near-branch case.
 template <typename T> __device__ __forceinline__ bool near_zero(T a, T lim) { return t_abs(a) < lim; }
 

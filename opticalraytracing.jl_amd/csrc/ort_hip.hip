@@ -82,7 +82,7 @@ enum { SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, S
        SL_TOFF, SL_TSQ, SL_AGG, SL_RES0, SL_RES1, SL_TAB0, SL_TAB1, SL_TAB2, SL_TAB3,
        SL_SB_FO, SL_SB_REC, SL_SB_MF, SL_SB_MR, SL_SB_TLF, SL_SB_TLR, SL_SB_AIN, SL_SB_AOUT, SL_SB_ENDS, SL_SB_FLAG,
        SL_SB_FIELDS, SL_SB_A, SL_SB_HP, SL_SB_PACK, SL_SB_CEXT, SL_SB_CREV, SL_FTSTATE, SL_FTTICKET, SL_FTERR, SL_FTDONE, SL_FTREADY, SL_DOMAIN, SL_RBSLOPES,
-       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_MTF_WS, SL_SPOT_WS, SL_GEO_CENTRE, SL_GEO_WS, SL_COUNT };
+       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_MTF_WS, SL_SPOT_WS, SL_GEO_CENTRE, SL_GEO_WS, SL_OPD_REFS, SL_OPD_WS, SL_COUNT };
 
 }  // namespace
 
@@ -127,6 +127,7 @@ struct ort_system {
     MerSurf* mer = nullptr;        // [nsys][S]
     std::vector<double> t_last;    // t[rows-1] per system (meridional ts tail)
     double* d_tlast = nullptr;     // the same on the device (aiming kernel)
+    double* n64 = nullptr;         // [nsys][rows] refractive indices as given (optical path: ort_opd_grid_f64)
     void* slab = nullptr;          // the one device allocation all of the above point into
     double* ap64 = nullptr;        // [nsys][S] squared clear semi-diameters (ort_system_set_apertures), or null
     float* ap32 = nullptr;
@@ -1381,6 +1382,81 @@ int spot_image_entry(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, co
     return ORT_OK;
 }
 
+// ---- wavefront OPD by optical path length (k_opd_*, ort_kernels.hpp) ----
+static_assert(sizeof(OpdRef) == sizeof(ort_opd_ref), "OpdRef mirrors ort_opd_ref");
+
+// the three launches; every pointer of `a` but the bundles / refs staged here is a device pointer already
+int opd_launch(ort_ctx* ctx, const ort_system* sys, int nb, const ort_opd_ref* refs, OpdArgs& a)
+{
+    const int64_t tiles = (int64_t)nb * a.tiles_per_bundle;
+    if (tiles > 0x7fffffffLL) return fail(ORT_EINVAL, "launch too large: %lld workgroups", (long long)tiles);
+    // refs: the caller's array may die with its frame — finish the copy before returning, as upload_bundles does
+    int rc = ctx->slot[SL_OPD_REFS].ensure((size_t)nb * sizeof(OpdRef)); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->slot[SL_OPD_REFS].p, refs, (size_t)nb * sizeof(OpdRef), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    a.refs = static_cast<const OpdRef*>(ctx->slot[SL_OPD_REFS].p);
+    // workspace: [reference slots | tile partials], both of 8-byte members
+    unsigned char* ws = nullptr;
+    rc = dev_out<unsigned char>(ctx, SL_OPD_WS, (size_t)nb * sizeof(OpdRefSlot) + (size_t)tiles * sizeof(OpdPart), &ws); if (rc) return rc;
+    a.ref_slot = reinterpret_cast<OpdRefSlot*>(ws);
+    a.part = reinterpret_cast<OpdPart*>(a.ref_slot + nb);
+    const bool poly = sys->arms64 >= ARMS_EVEN && sys->poly64;   // the batch carries polynomial rows: the build with their arm
+    if (poly) {
+        hipLaunchKernelGGL((k_opd_ref<true>), dim3((unsigned)nb), dim3(64), 0, ctx->stream, a);
+        hipLaunchKernelGGL((k_opd_grid<true>), dim3((unsigned)tiles), dim3(kOpdBlock), 0, ctx->stream, a);
+    } else {
+        hipLaunchKernelGGL((k_opd_ref<false>), dim3((unsigned)nb), dim3(64), 0, ctx->stream, a);
+        hipLaunchKernelGGL((k_opd_grid<false>), dim3((unsigned)tiles), dim3(kOpdBlock), 0, ctx->stream, a);
+    }
+    hipLaunchKernelGGL(k_opd_fold, dim3((unsigned)nb), dim3(kOpdBlock), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+    return ORT_OK;
+}
+
+int opd_grid_entry(ort_ctx* ctx, const ort_system* sys, int nb, const ort_bundle* bundles, const ort_opd_ref* refs,
+                   const double* axes, int64_t axes_len, int ny, int nx, double lambda, double* opd, int32_t* status,
+                   int64_t* count, double* mean, double* rms, double* pv, unsigned flags)
+{
+    int rc = check_ctx(ctx); if (rc) return rc;
+    rc = check_sys(ctx, sys); if (rc) return rc;
+    if (nb <= 0 || !bundles || !refs || !axes || ny <= 0 || nx <= 0 || !count || !rms) return fail(ORT_EINVAL, "bad opd_grid arguments");
+    if (!(lambda > 0.0)) return fail(ORT_EINVAL, "opd_grid: lambda %g is not positive", lambda);
+    if (flags & ORT_RAYBASIS) return fail(ORT_EINVAL, "opd_grid: ORT_RAYBASIS bundles have no launch wavefront (not built)");
+    const int64_t rpb = (int64_t)ny * nx;
+    if (rpb > 0x7fffffffLL - kTile) return fail(ORT_EINVAL, "bundle of %lld rays is too large (max 2^31)", (long long)rpb);
+    for (int b = 0; b < nb; ++b) {
+        if (bundles[b].stop == 0) return fail(ORT_EINVAL, "opd_grid: bundle %d has no stop", b);
+        if (!std::isfinite(refs[b].radius) || refs[b].radius == 0.0)
+            return fail(ORT_EINVAL, "opd_grid: bundle %d: radius %g is zero or not finite", b, refs[b].radius);
+    }
+    const int64_t N = rpb * nb;
+    OpdArgs a;
+    memset(&a, 0, sizeof a);
+    a.recs = sys->rec64; a.polys = sys->poly64; a.nidx = sys->n64; a.apert2 = sys->ap64;
+    a.S = sys->rows - 1; a.ny = ny; a.nx = nx; a.rpb = rpb; a.tiles_per_bundle = (int)((rpb + kOpdBlock - 1) / kOpdBlock);
+    a.lambda = lambda;
+    rc = upload_bundles<double>(ctx, sys, nb, bundles, ny, nx, axes_len, &a.bundles); if (rc) return rc;
+    if (flags & ORT_DEVICE_PTRS) {
+        a.axes = axes; a.opd = opd; a.status = status; a.count = count; a.mean = mean; a.rms = rms; a.pv = pv;
+        return opd_launch(ctx, sys, nb, refs, a);
+    }
+    rc = to_device<double>(ctx, SL_AXES, axes, (size_t)axes_len, &a.axes); if (rc) return rc;
+    if (opd) { rc = dev_out<double>(ctx, SL_OUT0, (size_t)N, &a.opd); if (rc) return rc; }
+    if (status) { rc = dev_out<int32_t>(ctx, SL_OUT3, (size_t)N, &a.status); if (rc) return rc; }
+    double* stats = nullptr;                                     // [count (as int64) | mean | rms | pv], nb each
+    rc = dev_out<double>(ctx, SL_OUT1, (size_t)4 * nb, &stats); if (rc) return rc;
+    a.count = reinterpret_cast<int64_t*>(stats); a.mean = stats + nb; a.rms = stats + 2 * nb; a.pv = stats + 3 * nb;
+    rc = opd_launch(ctx, sys, nb, refs, a); if (rc) return rc;
+    if (opd) { rc = from_device<double>(ctx, opd, a.opd, (size_t)N); if (rc) return rc; }
+    if (status) { rc = from_device<int32_t>(ctx, status, a.status, (size_t)N); if (rc) return rc; }
+    rc = from_device<int64_t>(ctx, count, a.count, (size_t)nb); if (rc) return rc;
+    if (mean) { rc = from_device<double>(ctx, mean, a.mean, (size_t)nb); if (rc) return rc; }
+    rc = from_device<double>(ctx, rms, a.rms, (size_t)nb); if (rc) return rc;
+    if (pv) { rc = from_device<double>(ctx, pv, a.pv, (size_t)nb); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ORT_OK;
+}
+
 }  // namespace
 
 // ======================================================================================
@@ -1674,6 +1750,13 @@ int ort_spot_image_f32(ort_ctx* ctx, int nb, int64_t cap, const int64_t* count, 
     return spot_image_entry<float>(ctx, nb, cap, count, ex, ey, scale, centre, nimg, dxi, image, lsf, outside, flags);
 }
 
+int ort_opd_grid_f64(ort_ctx* ctx, const ort_system* sys, int nb, const ort_bundle* bundles, const ort_opd_ref* refs,
+                     const double* axes, int64_t axes_len, int ny, int nx, double lambda, double* opd, int32_t* status,
+                     int64_t* count, double* mean, double* rms, double* pv, unsigned flags)
+{
+    return opd_grid_entry(ctx, sys, nb, bundles, refs, axes, axes_len, ny, nx, lambda, opd, status, count, mean, rms, pv, flags);
+}
+
 int ort_device_upload(ort_ctx* ctx, void* dst, const void* src, size_t bytes)
 {
     int rc = check_ctx(ctx); if (rc) return rc;
@@ -1736,7 +1819,8 @@ int ort_system_create(ort_ctx* ctx, int nsys, int rows, const double* R, const d
     const size_t b_r64 = pad(r64.size() * sizeof(SurfRec<double>)), b_r32 = pad(r32.size() * sizeof(SurfRec<float>));
     const size_t b_mer = pad(mer.size() * sizeof(MerSurf)), b_tl = pad(sys->t_last.size() * sizeof(double));
     const size_t b_c64 = pad(n_c64 * sizeof(double)), b_p64 = pad(p64.size() * sizeof(double)), b_p32 = pad(p32.size() * sizeof(float));
-    const size_t total = b_r64 + b_r32 + b_mer + b_tl + b_c64 + b_p64 + b_p32;
+    const size_t b_n64 = pad((size_t)nsys * rows * sizeof(double));
+    const size_t total = b_r64 + b_r32 + b_mer + b_tl + b_c64 + b_p64 + b_p32 + b_n64;
     std::vector<unsigned char> stage(total, 0);
     size_t o = 0;
     const size_t o_r64 = o; memcpy(stage.data() + o, r64.data(), r64.size() * sizeof(SurfRec<double>)); o += b_r64;
@@ -1746,6 +1830,7 @@ int ort_system_create(ort_ctx* ctx, int nsys, int rows, const double* R, const d
     const size_t o_c64 = o; if (ncoef > 0) memcpy(stage.data() + o, coef, n_c64 * sizeof(double)); o += b_c64;
     const size_t o_p64 = o; if (ncoef > 0) memcpy(stage.data() + o, p64.data(), p64.size() * sizeof(double)); o += b_p64;
     const size_t o_p32 = o; if (ncoef > 0) memcpy(stage.data() + o, p32.data(), p32.size() * sizeof(float)); o += b_p32;
+    const size_t o_n64 = o; memcpy(stage.data() + o, n, (size_t)nsys * rows * sizeof(double)); o += b_n64;
     {
         hipError_t e = hipMalloc(&sys->slab, total);
         if (e == hipSuccess) e = hipMemcpy(sys->slab, stage.data(), total, hipMemcpyHostToDevice);
@@ -1757,6 +1842,7 @@ int ort_system_create(ort_ctx* ctx, int nsys, int rows, const double* R, const d
         sys->rec32 = reinterpret_cast<SurfRec<float>*>(base + o_r32);
         sys->mer = reinterpret_cast<MerSurf*>(base + o_mer);
         sys->d_tlast = reinterpret_cast<double*>(base + o_tl);
+        sys->n64 = reinterpret_cast<double*>(base + o_n64);
         if (ncoef > 0) {
             sys->coef64 = reinterpret_cast<double*>(base + o_c64);
             sys->poly64 = reinterpret_cast<double*>(base + o_p64); sys->poly32 = reinterpret_cast<float*>(base + o_p32);

@@ -3937,6 +3937,214 @@ __global__ ORT_ZF_FN __launch_bounds__(kGeoBlock) void k_spot_image(GeoArgs<T> a
     }
 }
 
+// ------------------------------------------------------------------------------------
+// Wavefront OPD by optical path length (ort_opd_grid_f64): the grid trace carrying, beside the ray, the optical path it has
+// run — the quantity the Zernike chain above infers from transverse errors.  Positions come from the reference sequence
+// itself (surface_step_n<MATH_IEEE>: x, y and status bit-identical to k_trace); the path is accumulated AROUND each step from
+// the slopes and sags the step reads and leaves (opd_segment_excess, ort_device.hpp) in excess form: per ray
+//     E = n_0 (k0 x_L + k1 y_L) + sum_i n_i (d_i - t_i) + n' (tau h' + radius)
+// (launch term: the plane wavefront through the origin of the launch plane), and W = (E_ref - E) / lambda in waves.
+//   k_opd_ref        grid: bundles, one wave each, every lane tracing the bundle's reference ray (so a row's class stays
+//                    wave-uniform, as the step functions assume): E_ref, the resolved sphere centre and whether the bundle
+//                    has an OPD at all, to a workspace slot.
+//   k_opd_grid<POLY> grid: bundles x tiles of kOpdBlock rays, ONE ray per thread: 54 / 64 VGPRs (plain / POLY), 8 / 7 waves per
+//                    SIMD — the div / sqrt chains are hidden by occupancy where k_trace hides them by a second ray per
+//                    lane.  The bundle's SurfRec rows, its index row n[i], its squared apertures and (POLY) the rows'
+//                    pc | dc blocks are staged in LDS.  Each tile ends in a (n, mean, M2, min, max) reduction — a shuffle
+//                    tree per wave in lane order, the four waves in wave order — stored plainly to the tile's workspace slot.
+//   k_opd_fold       grid: bundles.  Thread t merges a contiguous run of tiles in tile order, the runs merge in one fixed
+//                    tree in run order: a function of the tile count alone — the same bits from run to run, and a bundle's
+//                    numbers never depend on what else is in the call.  No floating-point atomics anywhere.
+// ------------------------------------------------------------------------------------
+constexpr int kOpdBlock = 256;
+constexpr int kOpdWaves = kOpdBlock / 64;
+
+struct OpdRef { double y0, x0, px, py, radius; };             // ort_opd_ref (include/ort.h)
+struct OpdRefSlot { double E, px, py; int32_t ok, pad; };     // what k_opd_ref leaves per bundle
+struct OpdPart { double n, mean, m2, lo, hi; };               // rays, their mean, sum of squared deviations about it, extremes
+
+struct OpdArgs {
+    const SurfRec<double>* recs;     // [nsys][S]
+    const double* polys;             // [nsys][S][kPolyRec] or null
+    const double* nidx;              // [nsys][S + 1] refractive indices, row by row
+    const double* apert2;            // [nsys][S] or null
+    int S, ny, nx, tiles_per_bundle;
+    int64_t rpb;
+    const DevBundle<double>* bundles;
+    const OpdRef* refs;
+    const double* axes;
+    double lambda;
+    OpdRefSlot* ref_slot;            // [nb]
+    OpdPart* part;                   // [nb][tiles_per_bundle]
+    double* opd; int32_t* status;    // [nb][rpb] each, or null
+    int64_t* count; double *mean, *rms, *pv;
+};
+
+// Chan's pairwise update; `a` holds the earlier rays.  An empty side (n = 0, mean = 0) leaves the other's numbers exact.
+ORT_ZF_FN __device__ __forceinline__ OpdPart opd_merge(const OpdPart& a, const OpdPart& b)
+{
+    OpdPart r;
+    r.n = a.n + b.n;
+    const double inv = r.n > 0.0 ? 1.0 / r.n : 0.0, d = b.mean - a.mean;
+    r.mean = a.mean + d * (b.n * inv);
+    r.m2 = (a.m2 + b.m2) + (d * d) * ((a.n * b.n) * inv);
+    r.lo = fmin(a.lo, b.lo); r.hi = fmax(a.hi, b.hi);
+    return r;
+}
+
+// The workgroup's kOpdBlock partials (thread order = ray / run order) merged into one, valid in thread 0: per wave a
+// shuffle tree that always merges (lower lanes, higher lanes), then the waves in wave order.  Called by whole workgroups.
+ORT_ZF_FN __device__ __forceinline__ OpdPart opd_block_merge(OpdPart p, OpdPart (&s_part)[kOpdWaves], int tid)
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        OpdPart o;
+        o.n = __shfl_down(p.n, off); o.mean = __shfl_down(p.mean, off); o.m2 = __shfl_down(p.m2, off);
+        o.lo = __shfl_down(p.lo, off); o.hi = __shfl_down(p.hi, off);
+        p = opd_merge(p, o);                                     // (only lanes that are multiples of 2 off still matter)
+    }
+    if ((tid & 63) == 0) s_part[tid >> 6] = p;
+    __syncthreads();
+    OpdPart r = s_part[0];
+#pragma unroll
+    for (int w = 1; w < kOpdWaves; ++w) r = opd_merge(r, s_part[w]);
+    return r;
+}
+
+struct OpdRay { double xf, yf, u, v, xs, ys, E; int32_t st; };   // u, v: the slopes the ray arrives at the image plane with
+
+// One ray of bundle `bd` launched at (y, x) through the S rows at `rec` (LDS or global; polynomial blocks `pstride` values
+// apart, pc | dc first): positions and status exactly as k_trace's MATH_IEEE summary route forms them, E without the last leg.
+template <bool POLY>
+ORT_ZF_FN __device__ __forceinline__ OpdRay opd_trace_ray(const DevBundle<double>& bd, double y, double x,
+                                                          const SurfRec<double>* rec, const double* poly, int pstride,
+                                                          const double* nidx, const double* ap2, int S)
+{
+    Ray<double> ray[1];
+    ray[0].y = y; ray[0].x = x; ray[0].u = bd.u; ray[0].v = bd.v; ray[0].sprev = 0.0;
+    ray[0].k0 = bd.k0; ray[0].k1 = bd.k1; ray[0].k2 = bd.k2;
+    const int stop_u = __builtin_amdgcn_readfirstlane(bd.stop);
+    OpdRay o;
+    o.E = nidx[0] * (bd.k0 * x + bd.k1 * y);                     // launch term: k0 pairs with x, k1 with y (ray_init)
+    o.st = 1; o.xs = 0.0; o.ys = 0.0; o.u = bd.u; o.v = bd.v;
+    bool odd = false;
+    for (int i = 0; i < S; ++i) {
+        const SurfRec<double>& s = rec[i];
+        const int cls = __builtin_amdgcn_readfirstlane(s.cls);
+        o.u = ray[0].u; o.v = ray[0].v;
+        const double sp = ray[0].sprev;
+        surface_step_n<double, MATH_IEEE, 1, POLY ? ARMS_POLY : ARMS_GENERAL>(ray, s, POLY ? poly + i * pstride : nullptr, cls, i == S - 1, odd);
+        o.E += nidx[i] * opd_segment_excess(s.t, ray[0].sprev - sp, o.u, o.v);
+        o.st += __builtin_isunordered(ray[0].x, ray[0].y) ? 0 : 1;
+        if (i == stop_u) { o.xs = ray[0].x; o.ys = ray[0].y; }
+        if (ap2) {
+            const double r2 = ray[0].x * ray[0].x + ray[0].y * ray[0].y;
+            o.st |= (r2 > ap2[i]) ? kStatusVignetted : 0;
+            o.st += (o.st & kStatusVignetted) ? 0 : (1 << kStatusVigShift);
+        }
+    }
+    if (stop_u >= 0 && dev_hypot(o.xs, o.ys) > bd.a_stop) o.st |= 1 << 16;     // PupilSampling.jl:131-132
+    o.xf = ray[0].x; o.yf = ray[0].y;
+    return o;
+}
+
+// full_trace's filter (stop, clear apertures, a NaN hit)
+ORT_ZF_FN __device__ __forceinline__ bool opd_kept(const OpdRay& o)
+{
+    return !((o.st & ((1 << 16) | kStatusVignetted)) || t_isnan(o.xf) || t_isnan(o.yf));
+}
+
+template <bool POLY>
+__global__ ORT_ZF_FN __launch_bounds__(64) void k_opd_ref(OpdArgs a)
+{
+    const int b = blockIdx.x;
+    const DevBundle<double> bd = a.bundles[b];
+    const OpdRef rf = a.refs[b];
+    const int S = a.S;
+    const double* nidx = a.nidx + (int64_t)bd.system * (S + 1);
+    const OpdRay o = opd_trace_ray<POLY>(bd, rf.y0, rf.x0, a.recs + (int64_t)bd.system * S,
+                                         (POLY && a.polys) ? a.polys + (int64_t)bd.system * S * kPolyRec : nullptr, kPolyRec, nidx,
+                                         a.apert2 ? a.apert2 + (int64_t)bd.system * S : nullptr, S);
+    OpdRefSlot r;
+    const bool own = t_isnan(rf.px) || t_isnan(rf.py);           // NaN: the reference ray's own hit is the centre
+    r.px = own ? o.xf : rf.px; r.py = own ? o.yf : rf.py;
+    double leg;
+    const bool meets = opd_sphere_leg(o.xf - r.px, o.yf - r.py, o.u, o.v, rf.radius, leg);
+    r.ok = (opd_kept(o) && meets) ? 1 : 0; r.pad = 0;
+    r.E = o.E + nidx[S - 1] * leg;
+    if (threadIdx.x == 0) a.ref_slot[b] = r;
+}
+
+template <bool POLY>
+__global__ ORT_ZF_FN __launch_bounds__(kOpdBlock) void k_opd_grid(OpdArgs a)
+{
+    __shared__ SurfRec<double> s_rec[kMaxRows];
+    __shared__ __attribute__((aligned(16))) double s_poly[POLY ? kMaxRows * kPolyLds : 1];
+    __shared__ double s_n[kMaxRows], s_ap2[kMaxRows];
+    __shared__ OpdPart s_part[kOpdWaves];
+    const int tid = threadIdx.x, S = a.S;
+    const int b = blockIdx.x / a.tiles_per_bundle, tile = blockIdx.x - b * a.tiles_per_bundle;     // tiles never straddle bundles
+    const DevBundle<double> bd = a.bundles[b];
+    const int sysid = bd.system;
+    {   // stage this system's rows: records as 16-byte words, then the index row, the apertures and the polynomial blocks
+        constexpr int kW = sizeof(SurfRec<double>) / 16;
+        const uint4* src = reinterpret_cast<const uint4*>(a.recs + (int64_t)sysid * S);
+        uint4* dst = reinterpret_cast<uint4*>(s_rec);
+        for (int w = tid; w < S * kW; w += kOpdBlock) dst[w] = src[w];
+        if (tid < S) {
+            s_n[tid] = a.nidx[(int64_t)sysid * (S + 1) + tid];
+            s_ap2[tid] = a.apert2 ? a.apert2[(int64_t)sysid * S + tid] : 0.0;
+        }
+        if (POLY) {
+            const double* gpoly = a.polys + (int64_t)sysid * S * kPolyRec;
+            for (int w = tid; w < S * kPolyLds; w += kOpdBlock) {
+                const int row = w / kPolyLds, e = w - row * kPolyLds;
+                s_poly[w] = gpoly[row * kPolyRec + e];
+            }
+        }
+    }
+    __syncthreads();
+    const int64_t j = (int64_t)tile * kOpdBlock + tid;
+    const bool live = j < a.rpb;
+    const uint32_t jj = (uint32_t)(live ? j : a.rpb - 1);        // dead lanes retrace the bundle's last ray
+    const uint32_t iy = jj / (uint32_t)a.nx, ix = jj - iy * (uint32_t)a.nx;
+    const OpdRay o = opd_trace_ray<POLY>(bd, a.axes[bd.yoff + iy], a.axes[bd.xoff + ix], s_rec, s_poly, kPolyLds, s_n,
+                                         a.apert2 ? s_ap2 : nullptr, S);
+    const int64_t g = (int64_t)b * a.rpb + j;
+    if (live && a.status) a.status[g] = o.st;
+    const OpdRefSlot rs = a.ref_slot[b];
+    double leg;
+    const bool meets = opd_sphere_leg(o.xf - rs.px, o.yf - rs.py, o.u, o.v, a.refs[b].radius, leg);
+    const bool keep = live && rs.ok && meets && opd_kept(o);
+    const double W = (rs.E - (o.E + s_n[S - 1] * leg)) / a.lambda;
+    if (live && a.opd) __builtin_nontemporal_store(keep ? W : __builtin_nan(""), a.opd + g);
+    OpdPart p;
+    p.n = keep ? 1.0 : 0.0; p.mean = keep ? W : 0.0; p.m2 = 0.0;
+    p.lo = keep ? W : __builtin_inf(); p.hi = keep ? W : -__builtin_inf();
+    p = opd_block_merge(p, s_part, tid);
+    if (tid == 0) a.part[blockIdx.x] = p;
+}
+
+__global__ ORT_ZF_FN __launch_bounds__(kOpdBlock) void k_opd_fold(OpdArgs a)
+{
+    __shared__ OpdPart s_part[kOpdWaves];
+    const int tid = threadIdx.x, b = blockIdx.x, T = a.tiles_per_bundle;
+    const int run = (T + kOpdBlock - 1) / kOpdBlock;
+    const OpdPart* part = a.part + (int64_t)b * T;
+    OpdPart p;
+    p.n = 0.0; p.mean = 0.0; p.m2 = 0.0; p.lo = __builtin_inf(); p.hi = -__builtin_inf();
+    for (int t = tid * run; t < min(T, (tid + 1) * run); ++t) p = opd_merge(p, part[t]);
+    p = opd_block_merge(p, s_part, tid);
+    if (tid == 0) {
+        const bool ok = a.ref_slot[b].ok != 0, any = ok && p.n > 0.0;
+        const double nan = __builtin_nan("");
+        a.count[b] = ok ? (int64_t)p.n : -1;
+        a.rms[b] = any ? sqrt(p.m2 / p.n) : nan;
+        if (a.mean) a.mean[b] = any ? p.mean : nan;
+        if (a.pv) a.pv[b] = any ? p.hi - p.lo : nan;
+    }
+}
+
 #undef ORT_ZF_FN
 
 }  // namespace ort

@@ -186,6 +186,49 @@ class HipEngine:
                         "theta": th[b, :c].copy(), "rms": float(rms[b]), "count": c})
         return out
 
+    # ---- wavefront OPD by optical path length on the pupil grid ----
+    def opd_grid(self, pres: Prescription, bundles: Sequence[dict], refs: Sequence[dict], axes, ny: int, nx: int, lam: float,
+                 want_map: bool = True, want_status: bool = False) -> List[dict]:
+        """`ort_opd_grid_f64`: the optical path difference, in waves of `lam`, of every ray of the pupil-grid bundles of `grid`
+        against a reference sphere, by path length along the reference trace.  refs: one dict per bundle — y0, x0 (launch
+        point of the reference ray), px, py (centre of the sphere in the image plane; default NaN: the reference ray's own hit)
+        and radius (signed, image minus exit pupil).  `pres` ends in the image plane (`extended_prescription`).  Returns one
+        dict per bundle: opd [ny][nx] (NaN where the ray does not contribute; None without want_map), count, mean, rms, pv
+        (count -1 and NaN: the reference ray did not get through), and status [ny][nx] with want_status.  numpy axes go through
+        host buffers; a torch CUDA tensor of axes keeps every output on the device (torch tensors; the call is asynchronous
+        on the engine's stream)."""
+        nb, N = len(bundles), len(bundles) * ny * nx
+        if len(refs) != nb:
+            raise ValueError("opd_grid: one reference per bundle")
+        rarr = (_capi.ort_opd_ref * nb)()
+        for r, s in zip(rarr, refs):
+            r.y0, r.x0, r.radius = float(s["y0"]), float(s.get("x0", 0.0)), float(s["radius"])
+            r.px, r.py = float(s.get("px", np.nan)), float(s.get("py", np.nan))
+        if hasattr(axes, "data_ptr"):
+            import torch
+            new = lambda n, dt: torch.empty(n, dtype=dt, device=axes.device)
+            f8, i4, i8 = torch.float64, torch.int32, torch.int64
+            flags, naxes = self.base_flags | _capi.ORT_DEVICE_PTRS, axes.numel()
+        else:
+            axes = f64(axes).ravel()
+            new = lambda n, dt: np.empty(n, dtype=dt)
+            f8, i4, i8 = np.float64, np.int32, np.int64
+            flags, naxes = self.base_flags, axes.size
+        opd = new(N, f8) if want_map else None
+        status = new(N, i4) if want_status else None
+        count, mean, rms, pv = new(nb, i8), new(nb, f8), new(nb, f8), new(nb, f8)
+        sysd = self.system(pres)
+        check(self.ctx.lib.ort_opd_grid_f64(self.ctx.h, sysd.h, nb, _capi.make_bundles(bundles), rarr, ptr(axes), int(naxes), int(ny),
+                                            int(nx), float(lam), ptr(opd), ptr(status), ptr(count), ptr(mean), ptr(rms), ptr(pv), flags))
+        out = []
+        for b in range(nb):
+            d = {"opd": None if opd is None else opd[b * ny * nx:(b + 1) * ny * nx].reshape(ny, nx),
+                 "count": count[b], "mean": mean[b], "rms": rms[b], "pv": pv[b]}
+            if status is not None:
+                d["status"] = status[b * ny * nx:(b + 1) * ny * nx].reshape(ny, nx)
+            out.append(d)
+        return out
+
     # ---- wavegrad(eps, lambda): PupilSampling.jl:165-167 ------------------------------------
     def wavegrad(self, ex, ey, count, nu, lam: float, gx=None, gy=None):
         """`ort_wavegrad_f64`: (ex nu / lambda, ey nu / lambda) of nb full_trace slabs [nb][cap].  numpy arrays go through
