@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64, ort_mtf_f64, ort_spot_radii_f64 / _f32, ort_geo_mtf_f64 / _f32, ort_spot_image_f64 / _f32 and ort_opd_grid_f64: new entry points only, nothing existing moved)
+#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64, ort_mtf_f64, ort_spot_radii_f64 / _f32, ort_geo_mtf_f64 / _f32, ort_spot_image_f64 / _f32, ort_opd_grid_f64 and ort_psf_map_f64: new entry points only, nothing existing moved)
                                       0.4.1: ORT_FT_FUSED (full_trace's second pass inside the trace launch; bit-identical results) and its
                                       testing aid ort_ctx_test_fused_no_scan.  0.4.0: no new entry point; statistics-only full_trace walks tiles per workgroup (results within 1e-12 of
                                       0.3.0's); the device-side aiming loops trace without trigonometric calls only under ORT_FAST_MATH;
@@ -99,6 +99,8 @@ extern "C" {
                                        (decoupled look-back over the bundle's tiles) instead of staging compacted tiles in
                                        a workspace: 82 instead of 100 B/ray of HBM traffic, but tiles wait for their
                                        predecessors' counts — slower whenever the trace is VALU-bound */
+#define ORT_MAP_MIRROR_X  (1u << 11) /* ort_psf_map_f64: the map is the x >= 0 half of a pupil symmetric about x = 0 (column k at
+                                        x = k dpx); columns k >= 1 count a second time at -x_k */
 
 #define ORT_STATUS_STOPPED (1 << 16)
 #define ORT_STATUS_VIGNETTED (1 << 17)                /* ort_system_set_apertures: outside a clear aperture */
@@ -429,6 +431,41 @@ int ort_opd_grid_f64(ort_ctx *ctx, const ort_system *sys, int nb, const ort_bund
                      double *opd /* [nb][ny][nx] waves, or NULL */, int32_t *status /* [N] or NULL */,
                      int64_t *count /* [nb] */, double *mean, double *rms, double *pv /* [nb] each; mean/pv may be NULL */,
                      unsigned flags);
+/* Diffraction point-spread function and Strehl ratio of nb sampled wavefronts — OPD maps such as ort_opd_grid_f64 writes — with
+ * the pupil shape the map itself has: no polynomial truncation, and vignetted, clipped or obstructed pupils as they are (no
+ * reference counterpart).  The maps of many bundles are taken in one call and need never leave the device.
+ *  - opd[b][j][k] = W in waves at the pupil node (y_j, x_k) = (j dpy, k dpx): sign and layout of ort_opd_grid_f64's opd, which can
+ *    be passed unchanged.  step[b] = {dpy, dpx} in the normalised pupil coordinates in which an image displacement eps is
+ *    xi = eps nu / lambda (the units of wavegrad and of ort_psf_f64); a step may be negative for an axis that runs downward.
+ *    No origin is taken: it would multiply every image sample by a unit phase.
+ *  - a node contributes when its value is not NaN; N = number of contributing nodes of the bundle.
+ *  - image samples: xi_m = xi_c + (m - nimg / 2) dxi, eta the same; centre[b] = {xi_c, eta_c} — ort_psf_f64's grid.
+ *  - psf[b][my][mx] = | sum_nodes exp(i 2 pi (W - xi_mx x_k - eta_my y_j)) |^2 / N^2: a flat map of any shape gives exactly 1 at
+ *    xi = eta = 0, and a tilt W = 2 a x moves the peak to xi = +2 a.  Float64 matrix instructions form the double sum as
+ *    E_y P E_x^T; the twiddles are products of two sincospi values of directly formed arguments.
+ *  - ORT_MAP_MIRROR_X: the map is the x >= 0 half of a pupil symmetric about x = 0.  Columns k >= 1 contribute at -x_k too, with
+ *    the same W; column 0 counts once; N = 2 (contributing nodes) - (contributing nodes of column 0).  centre[b][0] is not read
+ *    and xi_c = 0 (the image of such a pupil is symmetric about xi = 0).  The result is that of the explicit [ny][2 nx - 1] map
+ *    without the flag.
+ *  - strehl[b] = the value at sample (nimg / 2, nimg / 2), always taken from one plain sum over the pupil in a fixed order:
+ *    bit-identical to psf[b][nimg / 2][nimg / 2], with or without psf, from run to run, with host or device pointers and under
+ *    every split of the work.  No floating-point atomics.
+ *  - count[b] = N.  A bundle with N = 0 (an all-NaN map, as ort_opd_grid_f64 writes for count = -1), or with a step that is zero
+ *    or not finite, gets NaN in psf[b] and strehl[b]; count[b] is still written and the call returns ORT_OK.
+ *  - psf == NULL: only strehl and count are computed — no matrix product.
+ * opd : [nb][ny][nx]; step : [nb][2]; centre : [nb][2] or NULL (zeros); psf : [nb][nimg][nimg] or NULL; strehl : [nb];
+ * count : [nb] or NULL.  Every pointer host or device per ORT_DEVICE_PTRS.
+ * ORT_EINVAL: ny or nx outside 1..2048, nimg not a multiple of 16 in 16..128, dxi <= 0 or NaN, nb < 0, NULL opd, step or
+ * strehl. */
+int ort_psf_map_f64(ort_ctx *ctx, int nb, int ny, int nx,
+                    const double *opd    /* [nb][ny][nx] waves; NaN = node outside the pupil */,
+                    const double *step   /* [nb][2] = {dpy, dpx} */,
+                    int nimg, double dxi,
+                    const double *centre /* [nb][2] = {xi_c, eta_c}, or NULL = 0 */,
+                    double *psf          /* [nb][nimg][nimg] or NULL */,
+                    double *strehl       /* [nb] */,
+                    int64_t *count       /* [nb] or NULL */,
+                    unsigned flags);
 /* Testing aid: shift the context's look-back ticket base against the device counter, the bookkeeping fault that
  * ort_full_trace_* with ORT_FT_LOOKBACK must report (ORT_EHIP; device-pointer callers see count = -1, rms = NaN). */
 int ort_ctx_test_skew_tickets(ort_ctx *ctx, int64_t delta);

@@ -27,6 +27,7 @@ ORT_FT_LOOKBACK = 1 << 7
 ORT_FT_FUSED = 1 << 10
 ORT_NO_SMALL_PATH = 1 << 8
 ORT_AIM_EDGE_AS_FOUND = 1 << 9
+ORT_MAP_MIRROR_X = 1 << 11
 ORT_STATUS_STOPPED = 1 << 16
 ORT_STATUS_VIGNETTED = 1 << 17
 ORT_MAX_ROWS = 64
@@ -143,6 +144,7 @@ SIGNATURES = {
     "ort_spot_image_f32": (_i, [_p, _i, _l, _p, _p, _p, _p, _p, _i, C.c_double, _p, _p, _p, _u]),
     "ort_opd_grid_f64": (_i, [_p, _p, _i, C.POINTER(ort_bundle), C.POINTER(ort_opd_ref), _p, _l, _i, _i, C.c_double,
                               _p, _p, _p, _p, _p, _p, _u]),
+    "ort_psf_map_f64": (_i, [_p, _i, _i, _i, _p, _p, _i, C.c_double, _p, _p, _p, _p, _u]),
     "ort_ctx_test_skew_tickets": (_i, [_p, _l]),
     "ort_ctx_test_fused_no_scan": (_i, [_p, _i]),
     "ort_aim_f64": (_i, [_p, _p, _p, _i, C.POINTER(ort_aim_in), C.POINTER(ort_aim_out), _u]),

@@ -975,6 +975,23 @@ def opd(system: System, H: float, k_rays: int = SPOT_RAYS, lam: float = LAMBDA, 
     return WavefrontOPD(r["opd"], yax, xax, int(r["count"]), float(r["mean"]), float(r["rms"]), float(r["pv"]))
 
 
+def psf_opd(system: System, H: float, k_rays: int = SPOT_RAYS, nimg: int = 64, dxi: float = 0.125, lam: float = LAMBDA, focus=None,
+            centre_eta: float = 0.0, engine=None):
+    """Diffraction point-spread function and Strehl ratio of one field straight from its wavefront map: `opd(system, H, k_rays,
+    lam, focus)`, then `ort_psf_map_f64` on that map with its real pupil shape (vignetting, clear apertures, obstructions) and
+    no polynomial truncation: (psf [nimg][nimg], strehl), sampled at (m - nimg / 2) dxi along xi and centre_eta + (m - nimg / 2)
+    dxi along eta, in wavegrad units as for `psf`.  The map is the x >= 0 half of the symmetric pupil (mirror_x).  Pupil
+    coordinates are the launch coordinates over y_EP, the half-width of the x axis (`full_trace_aim`'s y_EP): dpy =
+    (y[1] - y[0]) / y_EP and dpx = (x[1] - x[0]) / y_EP, so the sagittal semi-diameter of the launch grid is 1.  Many maps, or
+    device-resident ones: HipEngine.psf_map."""
+    eng = _eng(engine)
+    w = opd(system, H, k_rays, lam, focus, engine=eng)
+    y_EP = w.x[-1]
+    step = np.array([[(w.y[1] - w.y[0]) / y_EP, (w.x[1] - w.x[0]) / y_EP]])
+    p, s, _ = eng.psf_map(w.opd[None], step, nimg, dxi, centre=np.array([[0.0, float(centre_eta)]]), mirror_x=True)
+    return p[0], float(s[0])
+
+
 # ---------------------------------------------------------------------------------------
 # transfer matrix (TransferMatrix.jl)
 # ---------------------------------------------------------------------------------------

@@ -82,7 +82,7 @@ enum { SL_IN0 = 0, SL_IN1, SL_IN2, SL_IN3, SL_OUT0, SL_OUT1, SL_OUT2, SL_OUT3, S
        SL_TOFF, SL_TSQ, SL_AGG, SL_RES0, SL_RES1, SL_TAB0, SL_TAB1, SL_TAB2, SL_TAB3,
        SL_SB_FO, SL_SB_REC, SL_SB_MF, SL_SB_MR, SL_SB_TLF, SL_SB_TLR, SL_SB_AIN, SL_SB_AOUT, SL_SB_ENDS, SL_SB_FLAG,
        SL_SB_FIELDS, SL_SB_A, SL_SB_HP, SL_SB_PACK, SL_SB_CEXT, SL_SB_CREV, SL_FTSTATE, SL_FTTICKET, SL_FTERR, SL_FTDONE, SL_FTREADY, SL_DOMAIN, SL_RBSLOPES,
-       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_MTF_WS, SL_SPOT_WS, SL_GEO_CENTRE, SL_GEO_WS, SL_OPD_REFS, SL_OPD_WS, SL_COUNT };
+       SL_ZF_RHO, SL_ZF_THETA, SL_ZF_WS, SL_ZF_PART, SL_PSF_TW, SL_PSF_WS, SL_PSF_SUM, SL_MTF_WS, SL_SPOT_WS, SL_GEO_CENTRE, SL_GEO_WS, SL_OPD_REFS, SL_OPD_WS, SL_PSFMAP_CNT, SL_COUNT };
 
 }  // namespace
 
@@ -1049,6 +1049,76 @@ int psf_device(ort_ctx* ctx, int nb, int degree, const double* coef, const int32
     return ORT_OK;
 }
 
+// ---- PSF / Strehl ratio of OPD maps (k_psfmap_*, ort_kernels.hpp) ----
+// The PSF's rule with npanels = ceil(ny / 16): from 4 x CUs bundles on one workgroup per bundle, below that spans of panels.
+PsfPlan psfmap_plan(int nb, int ny, int nimg, int cus)
+{
+    PsfPlan pl;
+    pl.MT = nimg / 16;
+    pl.npanels = (ny + 15) / 16;
+    const int64_t target = 4 * (int64_t)std::max(cus, 1);
+    const int64_t spans = std::min<int64_t>(std::max<int64_t>((target + nb - 1) / nb, 1), pl.npanels);
+    pl.span_panels = (int)((pl.npanels + spans - 1) / spans);
+    pl.spans = (pl.npanels + pl.span_panels - 1) / pl.span_panels;
+    const size_t per_bundle = (size_t)pl.spans * 2 * nimg * nimg * sizeof(double);
+    pl.bundles_per_pass = pl.spans == 1 ? nb : (int)std::min<size_t>(std::max<size_t>(kZfWorkspaceBytes / per_bundle, 1), (size_t)nb);
+    pl.n2 = 0.0;                                                 // N belongs to the bundle: counted on the device
+    return pl;
+}
+
+template <int MT>
+int psfmap_launch_accumulate(hipStream_t st, unsigned grid, size_t lds, const PsfMapArgs& a)
+{
+    if constexpr (MT <= kPsfMaxMT) {
+        if (a.nimg != 16 * MT) return psfmap_launch_accumulate<MT + 1>(st, grid, lds, a);
+        auto launch = [&](auto kernel) {
+            if (lds + sizeof(PsfMapShared) > ((size_t)64 << 10))
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPsfBlock), lds, st, a);
+            return (int)ORT_OK;
+        };
+        return a.mirror ? launch(&k_psfmap_accumulate<MT, true>) : launch(&k_psfmap_accumulate<MT, false>);
+    }
+    return ORT_EINVAL;
+}
+
+// every pointer is a device pointer; centre, psf, count may be null
+int psfmap_device(ort_ctx* ctx, int nb, int ny, int nx, const double* opd, const double* step, int nimg, double dxi,
+                  const double* centre, double* psf, double* strehl, int64_t* count, bool mirror)
+{
+    if (nb == 0) return ORT_OK;
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const PsfPlan pl = psfmap_plan(nb, ny, nimg, cus);
+    const size_t plane = (size_t)nimg * nimg;
+    PsfMapArgs a;
+    a.b0 = 0; a.spans = pl.spans; a.span_panels = pl.span_panels; a.ny = ny; a.nx = nx; a.nimg = nimg; a.ld = psfmap_ld(nimg);
+    a.mirror = mirror ? 1 : 0; a.dxi = dxi; a.opd = opd; a.step = step; a.centre = centre;
+    a.ws = nullptr; a.psum = nullptr; a.pcnt = nullptr; a.psf = psf; a.strehl = strehl; a.count = count;
+    if (!psf) {                                                  // Strehl only: no tables, no matrix product
+        hipLaunchKernelGGL(k_psfmap_strehl, dim3((unsigned)nb), dim3(kPsfBlock), 0, ctx->stream, a);
+        HIP_TRY(hipGetLastError());
+        return ORT_OK;
+    }
+    int rc;
+    if (pl.spans > 1) {
+        rc = dev_out<double>(ctx, SL_PSF_WS, (size_t)pl.bundles_per_pass * pl.spans * 2 * plane, &a.ws); if (rc) return rc;
+        rc = dev_out<double>(ctx, SL_PSF_SUM, (size_t)pl.bundles_per_pass * pl.npanels * 2, &a.psum); if (rc) return rc;
+        rc = dev_out<int64_t>(ctx, SL_PSFMAP_CNT, (size_t)pl.bundles_per_pass * pl.spans, &a.pcnt); if (rc) return rc;
+    }
+    const size_t lds = psfmap_lds_doubles(nimg) * sizeof(double);
+    for (int b0 = 0; b0 < nb; b0 += pl.bundles_per_pass) {       // passes share the workspace: stream order keeps them apart
+        const int nbb = std::min(nb - b0, pl.bundles_per_pass);
+        a.b0 = b0;
+        rc = psfmap_launch_accumulate<1>(ctx->stream, (unsigned)nbb * (unsigned)pl.spans, lds, a); if (rc) return rc;
+        if (pl.spans > 1)
+            hipLaunchKernelGGL(k_psfmap_fold, dim3((unsigned)nbb * (unsigned)((plane + kPsfBlock - 1) / kPsfBlock)), dim3(kPsfBlock), 0,
+                               ctx->stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return ORT_OK;
+}
+
 // ---- tangential / sagittal OTF and MTF of Zernike wavefronts (k_mtf_*, ort_kernels.hpp) ----
 struct MtfPlan {
     int G;                   // block diagonals per wave: the instantiation
@@ -1755,6 +1825,32 @@ int ort_opd_grid_f64(ort_ctx* ctx, const ort_system* sys, int nb, const ort_bund
                      int64_t* count, double* mean, double* rms, double* pv, unsigned flags)
 {
     return opd_grid_entry(ctx, sys, nb, bundles, refs, axes, axes_len, ny, nx, lambda, opd, status, count, mean, rms, pv, flags);
+}
+
+int ort_psf_map_f64(ort_ctx* ctx, int nb, int ny, int nx, const double* opd, const double* step, int nimg, double dxi,
+                    const double* centre, double* psf, double* strehl, int64_t* count, unsigned flags)
+{
+    int rc = check_ctx(ctx); if (rc) return rc;
+    if (nb < 0 || !opd || !step || !strehl || !(dxi > 0.0)) return fail(ORT_EINVAL, "bad psf_map arguments");
+    if (ny < 1 || ny > kPsfMapMaxN || nx < 1 || nx > kPsfMapMaxN) return fail(ORT_EINVAL, "psf_map: map %d x %d outside 1..%d", ny, nx, kPsfMapMaxN);
+    if (nimg < 16 || nimg > 16 * kPsfMaxMT || nimg % 16) return fail(ORT_EINVAL, "psf_map: nimg %d is not a multiple of 16 in 16..%d", nimg, 16 * kPsfMaxMT);
+    const bool mirror = (flags & ORT_MAP_MIRROR_X) != 0;
+    if (nb == 0) return ORT_OK;
+    if ((flags & ORT_DEVICE_PTRS)) return psfmap_device(ctx, nb, ny, nx, opd, step, nimg, dxi, centre, psf, strehl, count, mirror);
+    const size_t plane = (size_t)nimg * nimg;
+    const double *dopd, *dstep, *dcentre = nullptr; double *dpsf = nullptr, *dstrehl; int64_t* dcount = nullptr;
+    rc = to_device<double>(ctx, SL_IN0, opd, (size_t)nb * ny * nx, &dopd); if (rc) return rc;
+    rc = to_device<double>(ctx, SL_IN1, step, (size_t)nb * 2, &dstep); if (rc) return rc;
+    if (centre) { rc = to_device<double>(ctx, SL_IN2, centre, (size_t)nb * 2, &dcentre); if (rc) return rc; }
+    if (psf) { rc = dev_out<double>(ctx, SL_OUT0, (size_t)nb * plane, &dpsf); if (rc) return rc; }
+    rc = dev_out<double>(ctx, SL_OUT1, (size_t)nb, &dstrehl); if (rc) return rc;
+    if (count) { rc = dev_out<int64_t>(ctx, SL_OUT2, (size_t)nb, &dcount); if (rc) return rc; }
+    rc = psfmap_device(ctx, nb, ny, nx, dopd, dstep, nimg, dxi, dcentre, dpsf, dstrehl, dcount, mirror); if (rc) return rc;
+    if (psf) { rc = from_device<double>(ctx, psf, dpsf, (size_t)nb * plane); if (rc) return rc; }
+    rc = from_device<double>(ctx, strehl, dstrehl, (size_t)nb); if (rc) return rc;
+    if (count) { rc = from_device<int64_t>(ctx, count, dcount, (size_t)nb); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ORT_OK;
 }
 
 int ort_device_upload(ort_ctx* ctx, void* dst, const void* src, size_t bytes)

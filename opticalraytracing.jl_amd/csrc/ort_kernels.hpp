@@ -4145,6 +4145,312 @@ __global__ ORT_ZF_FN __launch_bounds__(kOpdBlock) void k_opd_fold(OpdArgs a)
     }
 }
 
+
+// ------------------------------------------------------------------------------------
+// Diffraction PSF and Strehl ratio of sampled wavefronts — OPD maps — on the device (ort_psf_map_f64, include/ort.h).
+//
+// The map opd[b][j][k] holds W in waves at the pupil node (y_j, x_k) = (j dpy, k dpx), NaN where the node is outside the pupil;
+// N nodes contribute.  As in k_psf_*, psf = |U|^2 / N^2 with U = E_y P E_x^T, but P is loaded, the grid is ny x nx of any size,
+// and the steps belong to the bundle, so no table of E can be shared by the call.  With m' = m - nimg / 2 and k = k0 + kk:
+//     E_x[m][k] = exp(-i 2 pi m' dxi k dpx) = F_x(k0, m) A_x(kk, m)
+//     A_x(kk, m) = exp(-i 2 pi (m' dxi)(kk dpx)),  kk = 0 .. 15   the bundle's base table, built once per workgroup in LDS
+//     F_x(k0, m) = exp(-i 2 pi (m' dxi)(k0 dpx))                  nimg values, computed when the chunk k0 is entered
+// and the same for y with (j0, jj, dpy).  Both factors are sincospi of a directly formed product — no recurrence over m or k —
+// and THE CHUNK FACTOR IS APPLIED ON THE OPERAND: a lane forms its B (stage 1) or A (stage 2) value as one complex product
+// F A on the way from LDS to the matrix pipe.  (Applying F_x to a chunk's partial T tile would cost the same multiplications
+// but a second set of accumulators, and it could not make the mirrored operand real.)
+//
+//   k_psfmap_accumulate<MT, MIRROR>  the walk of k_psf_accumulate<MT>: 4 waves, 16-row panels, stage 1 T += P_chunk E_x^T per
+//                           16 x 16 chunk with P^T in LDS, stage 2 U += E_y,panel^T T with T straight from the accumulators,
+//                           wave w owning the image column tiles w, w + 4, ...  New: thread t loads node (row t / 16,
+//                           column t % 16) of the chunk — 16 consecutive doubles per 16 lanes — and takes one sincospi; NaN
+//                           and nodes past ny or nx give 0; a chunk without a contributing node is skipped by
+//                           __syncthreads_or, which doubles as the barrier that frees P's buffer; a panel without one skips
+//                           stage 2.  The count and the plain sum are taken in the same pass.  MIRROR (ORT_MAP_MIRROR_X):
+//                           P carries the column weight (1 for column 0, 2 otherwise) and the x operand is the real
+//                           Re(F_x A_x) = cos(2 pi m' dxi x_k): stage 1 issues two MFMAs per k-step and tile, not four.
+//                           One span per bundle: N is reduced at the end and |U|^2 / N^2 written at once.  Several: U goes
+//                           plainly to the span's workspace slot, its integer count beside it.
+//   k_psfmap_fold           counts and slots of a bundle summed in span order, |U|^2 / N^2
+//   k_psfmap_strehl         psf == NULL: count and plain sum alone, one workgroup per bundle, no LDS tables
+//
+// The centre sample is the plain sum of (weighted) P, as in k_psf_*: per panel each thread adds its nodes in chunk order, the
+// workgroup adds the threads in psf_reduce's fixed tree, and the panels are added in panel order by whoever holds them.  A
+// skipped chunk only omits adding +0, so all three routes give strehl[b] and the centre of psf[b] the same bits.
+// LDS (doubles): A_x, A_y as [part][16][ld], ld = nimg padded to an odd multiple of 16 so that the four 16-lane groups of an
+// operand read fall into different halves of the banks; then P^T [2][16][17], F_x [2][nimg], F_y [parity][2][nimg].
+// ------------------------------------------------------------------------------------
+constexpr int kPsfMapMaxN = 2048;             // ny, nx <= 2048
+constexpr int kPsfMapPld = 17;                // row stride of P^T in LDS: the transposing store of a 16-lane group hits 16 bank pairs
+
+struct PsfMapArgs {
+    int b0, spans, span_panels, ny, nx, nimg, ld, mirror;
+    double dxi;
+    const double* opd;                        // [nb][ny][nx]
+    const double* step;                       // [nb][2] = {dpy, dpx}
+    const double* centre;                     // [nb][2] or null
+    double* ws;                               // [bundle of the pass][span][2][nimg][nimg]
+    double* psum;                             // [bundle of the pass][panel][2]
+    int64_t* pcnt;                            // [bundle of the pass][span]
+    double *psf, *strehl;
+    int64_t* count;                           // [nb] or null
+};
+
+struct PsfMapShared {
+    double dpy, dpx, xc, yc;
+    double red[8];
+    int cnt[4];
+};
+
+ORT_ZF_FN __host__ __device__ inline int psfmap_ld(int nimg) { return nimg % 32 ? nimg : nimg + 16; }
+ORT_ZF_FN __host__ __device__ inline size_t psfmap_lds_doubles(int nimg)
+{
+    return (size_t)4 * 16 * psfmap_ld(nimg) + 2 * 16 * kPsfMapPld + 2 * nimg + 4 * nimg;
+}
+
+// Steps and centre of bundle b into LDS; returns whether the bundle's grid is usable (both steps finite and not zero).
+ORT_ZF_FN __device__ __forceinline__ bool psfmap_prepare(PsfMapShared& sh, const PsfMapArgs& a, int b, int tid)
+{
+    if (tid == 0) {
+        sh.dpy = a.step[2 * (size_t)b]; sh.dpx = a.step[2 * (size_t)b + 1];
+        sh.xc = (a.centre && !a.mirror) ? a.centre[2 * (size_t)b] : 0.0;
+        sh.yc = a.centre ? a.centre[2 * (size_t)b + 1] : 0.0;
+    }
+    __syncthreads();
+    return sh.dpy != 0.0 && sh.dpx != 0.0 && fabs(sh.dpy) < __builtin_inf() && fabs(sh.dpx) < __builtin_inf();
+}
+
+// exp(-i 2 pi (m' dxi) (k dp)): the one form of both twiddle factors
+ORT_ZF_FN __device__ __forceinline__ void psfmap_twiddle(int m, int nimg, double dxi, int k, double dp, double* re, double* im)
+{
+    sincospi(-2.0 * (((double)(m - nimg / 2) * dxi) * ((double)k * dp)), im, re);
+}
+
+// W at node (j, k) of bundle b and the node's weight: 0 = no contribution (past the map, or NaN), else 1, or 2 for a mirrored column.
+ORT_ZF_FN __device__ __forceinline__ int psfmap_load(const PsfMapArgs& a, int b, int j, int k, double* W)
+{
+    if (j >= a.ny || k >= a.nx) return 0;
+    *W = a.opd[((size_t)b * a.ny + j) * a.nx + k];
+    return *W == *W ? ((a.mirror && k > 0) ? 2 : 1) : 0;
+}
+
+// w exp(i 2 pi (W - xi_c x_k - eta_c y_j))
+ORT_ZF_FN __device__ __forceinline__ void psfmap_field(const PsfMapShared& sh, int w, double W, int j, int k, double* pr, double* pi)
+{
+    double s, c;
+    sincospi(2.0 * (W - sh.xc * ((double)k * sh.dpx) - sh.yc * ((double)j * sh.dpy)), &s, &c);
+    *pr = (double)w * c; *pi = (double)w * s;
+}
+
+// Sum of n over the workgroup (integers: any order).  Every thread returns the same value.
+ORT_ZF_FN __device__ __forceinline__ int psfmap_count(int n, int* cnt, int tid)
+{
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    if ((tid & 63) == 0) cnt[tid >> 6] = n;
+    __syncthreads();
+    return cnt[0] + cnt[1] + cnt[2] + cnt[3];
+}
+
+extern __shared__ double psfmap_lds[];
+
+// Grid: bundles of the pass x spans.  Dynamic LDS: psfmap_lds_doubles(nimg) doubles.
+template <int MT, bool MIRROR>
+__global__ ORT_ZF_FN __launch_bounds__(kPsfBlock, MT <= 4 ? 2 : 1) void k_psfmap_accumulate(PsfMapArgs a)
+{
+    constexpr int C = (MT + 3) / 4;                              // image column tiles per wave
+    constexpr int nimg = 16 * MT;
+    __shared__ PsfMapShared sh;
+    const int ld = a.ld;
+    double* const Axr = psfmap_lds;                              // [16][ld] each
+    double* const Axi = Axr + 16 * ld;
+    double* const Ayr = Axi + 16 * ld;
+    double* const Ayi = Ayr + 16 * ld;
+    double* const Pre = Ayi + 16 * ld;                           // P^T of the chunk: [column][kPsfMapPld]
+    double* const Pim = Pre + 16 * kPsfMapPld;
+    double* const Fx = Pim + 16 * kPsfMapPld;                    // [2][nimg]
+    double* const Fy = Fx + 2 * nimg;                            // [panel parity][2][nimg]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int bl = blockIdx.x / a.spans, span = blockIdx.x - bl * a.spans, b = a.b0 + bl;
+    const int npanels = (a.ny + 15) / 16;
+    const bool direct = a.spans == 1;
+    const int p_lo = span * a.span_panels, p_hi = min(p_lo + a.span_panels, npanels);
+    const bool ok = psfmap_prepare(sh, a, b, tid);
+    const int g = lane >> 4, l15 = lane & 15;                    // the row of a k-step this lane holds; its column of a tile
+    const int nr = tid >> 4, nc = tid & 15;                      // this thread's node of a chunk: row, column
+    if (ok)
+        for (int e = tid; e < 16 * nimg; e += kPsfBlock) {       // the base tables (visible after the first chunk's vote)
+            const int kk = e / nimg, m = e - kk * nimg;
+            psfmap_twiddle(m, nimg, a.dxi, kk, sh.dpx, Axr + kk * ld + m, Axi + kk * ld + m);
+            psfmap_twiddle(m, nimg, a.dxi, kk, sh.dpy, Ayr + kk * ld + m, Ayi + kk * ld + m);
+        }
+    bool on[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) on[c] = (MT % 4 == 0 || c < C - 1) ? true : wave + 4 * c < MT;      // only a last, partial round of tiles can lack a wave
+    zf_d4 Ur[C][MT], Ui[C][MT];
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) { Ur[c][m] = zf_d4{0.0, 0.0, 0.0, 0.0}; Ui[c][m] = zf_d4{0.0, 0.0, 0.0, 0.0}; }
+    double sr = 0.0, si = 0.0;                                   // the plain sum of the panels so far (direct route)
+    int n = 0;                                                   // this thread's weighted node count
+    for (int p = p_lo; p < p_hi; ++p) {
+        const int j0 = 16 * p;
+        double* const fy = Fy + (p & 1) * 2 * nimg;              // two buffers: a wave may enter panel p + 1 while another is in stage 2 of p
+        if (ok && tid < nimg) psfmap_twiddle(tid, nimg, a.dxi, j0, sh.dpy, fy + tid, fy + nimg + tid);
+        zf_d4 Tr[C], Ti[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) { Tr[c] = zf_d4{0.0, 0.0, 0.0, 0.0}; Ti[c] = zf_d4{0.0, 0.0, 0.0, 0.0}; }
+        double qr = 0.0, qi = 0.0;
+        bool filled = false;
+        for (int k0 = 0; k0 < a.nx; k0 += 16) {
+            double W = 0.0;
+            const int w = psfmap_load(a, b, j0 + nr, k0 + nc, &W);
+            n += w;
+            if (!__syncthreads_or(w) || !ok) continue;           // uniform; also: the previous chunk's readers are done
+            filled = true;
+            double pr = 0.0, pi = 0.0;
+            if (w) psfmap_field(sh, w, W, j0 + nr, k0 + nc, &pr, &pi);
+            qr += pr; qi += pi;
+            Pre[nc * kPsfMapPld + nr] = pr; Pim[nc * kPsfMapPld + nr] = pi;
+            if (tid < nimg) psfmap_twiddle(tid, nimg, a.dxi, k0, sh.dpx, Fx + tid, Fx + nimg + tid);
+            __syncthreads();
+            // stage 1: T += P E_x^T.  A[i][k] = P[j0 + i][k0 + 4 ks + k] (lane = 16 k + i), B[k][n] = E_x[16 mt + n][k0 + 4 ks + k]
+            double fr[C], fi[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const int col = on[c] ? 16 * (wave + 4 * c) + l15 : 0;
+                fr[c] = Fx[col]; fi[c] = Fx[nimg + col];
+            }
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const double ar = Pre[(4 * ks + g) * kPsfMapPld + l15], ai = Pim[(4 * ks + g) * kPsfMapPld + l15];
+                const int row = (4 * ks + g) * ld + l15;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    if (!on[c]) continue;
+                    const int col = 16 * (wave + 4 * c);
+                    const double br = Axr[row + col], bi = Axi[row + col];
+                    const double er = __builtin_fma(fr[c], br, -(fi[c] * bi));
+                    Tr[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, er, Tr[c], 0, 0, 0);
+                    if constexpr (MIRROR) {                      // the operand is real: w cos(2 pi m' dxi x_k), w in P
+                        Ti[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, er, Ti[c], 0, 0, 0);
+                    } else {
+                        const double ei = __builtin_fma(fr[c], bi, fi[c] * br);
+                        Tr[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(-ai, ei, Tr[c], 0, 0, 0);
+                        Ti[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, ei, Ti[c], 0, 0, 0);
+                        Ti[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, er, Ti[c], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        psf_reduce(qr, qi, sh.red, tid);
+        if (direct) { sr += qr; si += qi; }
+        else if (tid == 0) { double* q = a.psum + 2 * ((size_t)bl * npanels + p); q[0] = qr; q[1] = qi; }
+        if (!filled) continue;                                   // uniform: T = 0
+        // stage 2: U += E_y,panel^T T.  A[i][k] = E_y[16 mty + i][j0 + 4 ks + k]; B[k][n] = T[4 ks + k][n] = register ks of the T tile
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            const double gr = fy[16 * m + l15], gi = fy[nimg + 16 * m + l15];
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int at = (4 * ks + g) * ld + 16 * m + l15;
+                const double br = Ayr[at], bi = Ayi[at];
+                const double er = __builtin_fma(gr, br, -(gi * bi)), ei = __builtin_fma(gr, bi, gi * br), nei = -ei;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    if (!on[c]) continue;
+                    Ur[c][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(er, Tr[c][ks], Ur[c][m], 0, 0, 0);
+                    Ur[c][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(nei, Ti[c][ks], Ur[c][m], 0, 0, 0);
+                    Ui[c][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(er, Ti[c][ks], Ui[c][m], 0, 0, 0);
+                    Ui[c][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(ei, Tr[c][ks], Ui[c][m], 0, 0, 0);
+                }
+            }
+        }
+    }
+    const int N = psfmap_count(n, sh.cnt, tid);
+    // element (my, mx) = (16 m + 4 v + lane / 16, 16 (wave + 4 c) + lane % 16) is register v of tile [c][m]
+    const double nan = __builtin_nan("");
+    const bool some = ok && N > 0;
+    const double n2 = (double)N * (double)N;
+    const size_t plane = (size_t)nimg * nimg;
+    const int centre = (nimg / 2) * nimg + nimg / 2;
+    double* slot = a.ws + ((size_t)bl * a.spans + span) * 2 * plane;
+    double* out = a.psf + (size_t)b * plane;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (!on[c]) continue;
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int e = (16 * m + 4 * v + g) * nimg + 16 * (wave + 4 * c) + l15;
+                if (!direct) { slot[e] = Ur[c][m][v]; slot[plane + e] = Ui[c][m][v]; }
+                else if (e != centre) out[e] = some ? psf_intensity(Ur[c][m][v], Ui[c][m][v], n2) : nan;
+            }
+    }
+    if (tid == 0) {
+        if (direct) {
+            const double s = some ? psf_intensity(sr, si, n2) : nan;
+            out[centre] = s; a.strehl[b] = s;
+            if (a.count) a.count[b] = N;
+        } else a.pcnt[(size_t)bl * a.spans + span] = N;
+    }
+}
+
+// Grid: bundles of the pass x ceil(nimg^2 / 256), one thread per image sample.
+__global__ ORT_ZF_FN __launch_bounds__(kPsfBlock) void k_psfmap_fold(PsfMapArgs a)
+{
+    const size_t plane = (size_t)a.nimg * a.nimg;
+    const int per = (int)((plane + kPsfBlock - 1) / kPsfBlock);
+    const int bl = blockIdx.x / per, b = a.b0 + bl, npanels = (a.ny + 15) / 16;
+    const int e = (blockIdx.x - bl * per) * kPsfBlock + threadIdx.x;
+    if (e >= (int)plane) return;
+    const double dpy = a.step[2 * (size_t)b], dpx = a.step[2 * (size_t)b + 1];
+    int64_t N = 0;
+    for (int s = 0; s < a.spans; ++s) N += a.pcnt[(size_t)bl * a.spans + s];
+    const bool some = dpy != 0.0 && dpx != 0.0 && fabs(dpy) < __builtin_inf() && fabs(dpx) < __builtin_inf() && N > 0;
+    const bool centre = e == (a.nimg / 2) * a.nimg + a.nimg / 2;
+    double re = 0.0, im = 0.0;
+    if (some && centre) {
+        const double* q = a.psum + 2 * (size_t)bl * npanels;
+        for (int p = 0; p < npanels; ++p) { re += q[2 * p]; im += q[2 * p + 1]; }
+    } else if (some) {
+        const double* slot = a.ws + (size_t)bl * a.spans * 2 * plane + e;
+        for (int s = 0; s < a.spans; ++s) { re += slot[(size_t)s * 2 * plane]; im += slot[(size_t)s * 2 * plane + plane]; }
+    }
+    const double val = some ? psf_intensity(re, im, (double)N * (double)N) : __builtin_nan("");
+    a.psf[(size_t)b * plane + e] = val;
+    if (centre) { a.strehl[b] = val; if (a.count) a.count[b] = N; }
+}
+
+// The psf == NULL route.  Grid: bundles.
+__global__ ORT_ZF_FN __launch_bounds__(kPsfBlock) void k_psfmap_strehl(PsfMapArgs a)
+{
+    __shared__ PsfMapShared sh;
+    const int tid = threadIdx.x, b = a.b0 + blockIdx.x, nr = tid >> 4, nc = tid & 15;
+    const bool ok = psfmap_prepare(sh, a, b, tid);
+    double sr = 0.0, si = 0.0;
+    int n = 0;
+    for (int j0 = 0; j0 < a.ny; j0 += 16) {
+        double qr = 0.0, qi = 0.0;
+        for (int k0 = 0; k0 < a.nx; k0 += 16) {
+            double W = 0.0, pr, pi;
+            const int w = psfmap_load(a, b, j0 + nr, k0 + nc, &W);
+            n += w;
+            if (!w || !ok) continue;
+            psfmap_field(sh, w, W, j0 + nr, k0 + nc, &pr, &pi);
+            qr += pr; qi += pi;
+        }
+        psf_reduce(qr, qi, sh.red, tid);
+        sr += qr; si += qi;
+    }
+    const int N = psfmap_count(n, sh.cnt, tid);
+    if (tid == 0) {
+        a.strehl[b] = (ok && N > 0) ? psf_intensity(sr, si, (double)N * (double)N) : __builtin_nan("");
+        if (a.count) a.count[b] = N;
+    }
+}
+
 #undef ORT_ZF_FN
 
 }  // namespace ort

@@ -299,6 +299,35 @@ class HipEngine:
                                        None if psf is None else ptr(psf), ptr(strehl), flags))
         return psf, strehl
 
+    # ---- diffraction PSF / Strehl ratio of OPD maps ----
+    def psf_map(self, opd, step, nimg: int, dxi: float, centre=None, mirror_x: bool = False, want_psf: bool = True):
+        """`ort_psf_map_f64`: the point-spread function [nb][nimg][nimg] and the Strehl ratio [nb] of the sampled wavefronts
+        opd [nb][ny][nx] (waves, NaN = node outside the pupil: the maps of `opd_grid`), node (j, k) at (j dpy, k dpx) with
+        step [nb][2] = (dpy, dpx) in wavegrad units, sampled at xi = centre + (m - nimg / 2) dxi.  mirror_x: the maps are the
+        x >= 0 half of a pupil symmetric about x = 0 (centre[:, 0] is then ignored).  Returns (psf or None, strehl, count);
+        count [nb] is the number of contributing nodes, and a bundle without any, or with a zero or non-finite step, gives NaN.
+        numpy arrays go through host buffers; torch CUDA tensors (opd, step, and centre when given) stay on the device — the
+        call is asynchronous on the engine's stream and the results are torch tensors."""
+        nb, ny, nx = opd.shape
+        if hasattr(opd, "data_ptr"):
+            import torch
+            psf = torch.empty((nb, nimg, nimg), dtype=torch.float64, device=opd.device) if want_psf else None
+            strehl = torch.empty(nb, dtype=torch.float64, device=opd.device)
+            count = torch.empty(nb, dtype=torch.int64, device=opd.device)
+            flags = self.base_flags | _capi.ORT_DEVICE_PTRS
+        else:
+            opd, step = f64(opd), f64(step)
+            centre = None if centre is None else f64(centre)
+            psf = np.empty((nb, nimg, nimg)) if want_psf else None
+            strehl, count = np.empty(nb), np.empty(nb, dtype=np.int64)
+            flags = self.base_flags
+        if mirror_x:
+            flags |= _capi.ORT_MAP_MIRROR_X
+        check(self.ctx.lib.ort_psf_map_f64(self.ctx.h, int(nb), int(ny), int(nx), ptr(opd), ptr(step), int(nimg), float(dxi),
+                                           None if centre is None else ptr(centre), None if psf is None else ptr(psf),
+                                           ptr(strehl), ptr(count), flags))
+        return psf, strehl, count
+
     # ---- tangential / sagittal OTF and MTF of Zernike wavefronts ----
     def mtf(self, coef, degree: int, npupil: int, info=None, want_otf: bool = False):
         """`ort_mtf_f64`: the modulus transfer function [nb][2][npupil] of the wavefronts whose Zernike coefficients are coef
