@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64, ort_mtf_f64, ort_spot_radii_f64 / _f32, ort_geo_mtf_f64 / _f32, ort_spot_image_f64 / _f32, ort_opd_grid_f64 and ort_psf_map_f64: new entry points only, nothing existing moved)
+#define ORT_VERSION 401            /* (unchanged by the additions ort_zernike_fit_f64, ort_psf_f64, ort_mtf_f64, ort_spot_radii_f64 / _f32, ort_geo_mtf_f64 / _f32, ort_spot_image_f64 / _f32, ort_opd_grid_f64, ort_psf_map_f64 and ort_mtf_map_f64: new entry points only, nothing existing moved)
                                       0.4.1: ORT_FT_FUSED (full_trace's second pass inside the trace launch; bit-identical results) and its
                                       testing aid ort_ctx_test_fused_no_scan.  0.4.0: no new entry point; statistics-only full_trace walks tiles per workgroup (results within 1e-12 of
                                       0.3.0's); the device-side aiming loops trace without trigonometric calls only under ORT_FAST_MATH;
@@ -99,7 +99,7 @@ extern "C" {
                                        (decoupled look-back over the bundle's tiles) instead of staging compacted tiles in
                                        a workspace: 82 instead of 100 B/ray of HBM traffic, but tiles wait for their
                                        predecessors' counts — slower whenever the trace is VALU-bound */
-#define ORT_MAP_MIRROR_X  (1u << 11) /* ort_psf_map_f64: the map is the x >= 0 half of a pupil symmetric about x = 0 (column k at
+#define ORT_MAP_MIRROR_X  (1u << 11) /* ort_psf_map_f64, ort_mtf_map_f64: the map is the x >= 0 half of a pupil symmetric about x = 0 (column k at
                                         x = k dpx); columns k >= 1 count a second time at -x_k */
 
 #define ORT_STATUS_STOPPED (1 << 16)
@@ -465,6 +465,40 @@ int ort_psf_map_f64(ort_ctx *ctx, int nb, int ny, int nx,
                     double *psf          /* [nb][nimg][nimg] or NULL */,
                     double *strehl       /* [nb] */,
                     int64_t *count       /* [nb] or NULL */,
+                    unsigned flags);
+/* Sagittal and tangential optical transfer function (OTF) and its modulus (MTF) of nb sampled wavefronts — OPD maps — with the
+ * pupil shape the map itself has: the exact autocorrelation of the sampled pupil field, the direct counterpart of ort_mtf_f64 as
+ * ort_psf_map_f64 is of ort_psf_f64 (no reference counterpart).
+ *  - opd, step, the contributing-node rule (not NaN) and ORT_MAP_MIRROR_X are exactly those of ort_psf_map_f64: a map written
+ *    by ort_opd_grid_f64 is passed unchanged.  P[j][k] = exp(i 2 pi W[j][k]) on contributing nodes, 0 elsewhere and outside the
+ *    grid; N = number of contributing nodes.
+ *  - ORT_MAP_MIRROR_X: the pupil is the explicit [ny][2 nx - 1] map, columns k >= 1 repeated at -x_k; N by ort_psf_map_f64's
+ *    rule; every output equals the output for that explicit map without the flag.
+ *  - axis 0 shears along x by d nodes: H_0(d) = (1 / N) sum P(x + d |dpx|, y) conj(P(x, y)); axis 1 the same along y with
+ *    |dpy|; d = 0 .. nshear - 1.  The shear is a physical displacement, not an index displacement: for a negative step the
+ *    index shear runs the other way and the result is the conjugate of the index-shear sum.
+ *  - sign: a tilt W = 2 a x gives arg H_0(d) = +2 pi 2 a d |dpx| whatever the sign of dpx — ort_mtf_f64's sign (whose step is
+ *    2 / npupil), consistent with the PSF peak at xi = +2 a.  H(0) = 1 to rounding.
+ *  - sample d of axis 0 lies at d |dpx| cycles per unit of xi (wavegrad units), sample d of axis 1 at d |dpy|; multiply by
+ *    |nu| / lambda for cycles per length unit.  For a field along y, axis 0 is the sagittal curve and axis 1 the tangential one.
+ *  - otf[b][axis][d] = {Re H, Im H}, mtf[b][axis][d] = |H|: mtf is hypot() of exactly the two numbers written to otf, as for
+ *    ort_mtf_f64.  A sample with d at or beyond the width of its axis — nx, or 2 nx - 1 mirrored, on axis 0; ny on axis 1 —
+ *    is written as exactly +0 in otf and mtf.
+ *  - count[b] = N always.  A bundle with N = 0, or with a step that is zero or not finite, gets NaN in all its otf and mtf
+ *    samples; the call returns ORT_OK.
+ *  - no floating-point atomics and a fixed summation order: the same call gives the same bits from run to run and with host
+ *    or device pointers.  Float64 matrix instructions accumulate the Gram tiles of the pupil's lines.
+ * opd : [nb][ny][nx]; step : [nb][2]; otf : [nb][2][nshear][2] or NULL; mtf : [nb][2][nshear] or NULL; count : [nb] or NULL.
+ * Every pointer host or device per ORT_DEVICE_PTRS.
+ * ORT_EINVAL: ny or nx outside 1..2048, nx > 1024 under ORT_MAP_MIRROR_X (the mirrored row is one line in LDS), nshear outside
+ * 1..2048, nb < 0, NULL opd or step, otf and mtf both NULL. */
+int ort_mtf_map_f64(ort_ctx *ctx, int nb, int ny, int nx,
+                    const double *opd   /* [nb][ny][nx] waves; NaN = node outside the pupil */,
+                    const double *step  /* [nb][2] = {dpy, dpx} */,
+                    int nshear,
+                    double *otf         /* [nb][2][nshear][2] or NULL */,
+                    double *mtf         /* [nb][2][nshear] or NULL */,
+                    int64_t *count      /* [nb] or NULL */,
                     unsigned flags);
 /* Testing aid: shift the context's look-back ticket base against the device counter, the bookkeeping fault that
  * ort_full_trace_* with ORT_FT_LOOKBACK must report (ORT_EHIP; device-pointer callers see count = -1, rms = NaN). */

@@ -21,7 +21,7 @@ from .api import (  # noqa: F401
     full_trace_aim_batch, full_trace_batch, full_trace_grid, reversed_layout, incidences, linrange, linrange_batch, raytrace, reverse_transfer, sag, solve, surface_ray,
     surface_to_focus, trace_chief_ray, trace_marginal_ray, transfer, transfer_real, wavegrad, refract,
     zernike_fit, zernike_terms, psf, mtf, mtf_frequencies, spot_radii, geo_mtf, spot_image,
-    opd, WavefrontOPD, psf_opd,
+    opd, WavefrontOPD, psf_opd, mtf_opd,
 )
 from .analysis import SA, TSA, Aberration, aberrations, caustic_rays  # noqa: F401
 from .engine import HipEngine, Prescription, default_engine, set_default_engine  # noqa: F401

@@ -145,6 +145,7 @@ SIGNATURES = {
     "ort_opd_grid_f64": (_i, [_p, _p, _i, C.POINTER(ort_bundle), C.POINTER(ort_opd_ref), _p, _l, _i, _i, C.c_double,
                               _p, _p, _p, _p, _p, _p, _u]),
     "ort_psf_map_f64": (_i, [_p, _i, _i, _i, _p, _p, _i, C.c_double, _p, _p, _p, _p, _u]),
+    "ort_mtf_map_f64": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p, _p, _u]),
     "ort_ctx_test_skew_tickets": (_i, [_p, _l]),
     "ort_ctx_test_fused_no_scan": (_i, [_p, _i]),
     "ort_aim_f64": (_i, [_p, _p, _p, _i, C.POINTER(ort_aim_in), C.POINTER(ort_aim_out), _u]),

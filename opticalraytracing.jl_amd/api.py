@@ -992,6 +992,24 @@ def psf_opd(system: System, H: float, k_rays: int = SPOT_RAYS, nimg: int = 64, d
     return p[0], float(s[0])
 
 
+def mtf_opd(system: System, H: float, k_rays: int = SPOT_RAYS, lam: float = LAMBDA, focus=None, nshear=None, engine=None):
+    """Sagittal and tangential MTF of one field straight from its wavefront map: `opd(system, H, k_rays, lam, focus)`, then
+    `ort_mtf_map_f64` on that half map (mirror_x) with its real pupil shape and no polynomial truncation: (freq_sagittal,
+    mtf_sagittal, freq_tangential, mtf_tangential).  The steps are `psf_opd`'s — launch coordinates over y_EP — and sample d
+    lies at d |dpx| (sagittal) and d |dpy| (tangential) cycles per wavegrad unit; nshear defaults to max(ny, 2 nx - 1), every
+    shear either axis has, and samples past an axis's width are 0.  Many maps, device-resident ones or the complex OTF:
+    HipEngine.mtf_map."""
+    eng = _eng(engine)
+    w = opd(system, H, k_rays, lam, focus, engine=eng)
+    y_EP = w.x[-1]
+    step = np.array([[(w.y[1] - w.y[0]) / y_EP, (w.x[1] - w.x[0]) / y_EP]])
+    ny, nx = w.opd.shape
+    nshear = max(ny, 2 * nx - 1) if nshear is None else int(nshear)
+    m, _, _ = eng.mtf_map(w.opd[None], step, nshear, mirror_x=True)
+    d = np.arange(nshear)
+    return d * abs(step[0, 1]), m[0, 0], d * abs(step[0, 0]), m[0, 1]
+
+
 # ---------------------------------------------------------------------------------------
 # transfer matrix (TransferMatrix.jl)
 # ---------------------------------------------------------------------------------------

@@ -1188,6 +1188,109 @@ int mtf_device(ort_ctx* ctx, int nb, int degree, const double* coef, const int32
     return ORT_OK;
 }
 
+// ---- sagittal / tangential OTF and MTF of OPD maps (k_mtfmap_*, ort_kernels.hpp) ----
+struct MtfMapPlan {
+    int G;                   // block diagonals per wave: the instantiation, from the axis that needs more tiles
+    int nd[2], ng[2], ld[2]; // per axis: tiles accumulated, groups of 4 G of them sharing one, LDS line stride in doubles
+    int spans, span_steps;   // workgroups per (bundle, axis, group), k-steps of 4 lines per workgroup (a multiple of 4)
+    int stage_steps;         // k-steps per LDS stage
+    size_t lds_bytes;
+    int bundles_per_pass;    // bundles whose offset sums fit the workspace (spans > 1 only)
+};
+
+// Plain integer arithmetic, usable in a constant expression: the limits are checked below without a device.
+constexpr MtfMapPlan mtfmap_plan(int nb, int ny, int nx, int nshear, bool mirror, int cus)
+{
+    MtfMapPlan pl{};
+    const int width[2] = {mirror ? 2 * nx - 1 : nx, ny}, lines[2] = {ny, nx}, nsb = (nshear + 15) / 16;
+    for (int ax = 0; ax < 2; ++ax) {
+        const int nblk = (width[ax] + 15) / 16;
+        pl.nd[ax] = nblk < nsb + 1 ? nblk : nsb + 1;             // sample block D needs the tiles D and D + 1
+        pl.ld[ax] = 16 * (nblk | 1) + ax;                        // axis 0: an odd number of 16-double blocks, as k_mtf_*; axis 1: odd,
+    }                                                            // for the transposing store
+    const int ndmax = pl.nd[0] > pl.nd[1] ? pl.nd[0] : pl.nd[1], ldmax = pl.ld[0] > pl.ld[1] ? pl.ld[0] : pl.ld[1];
+    pl.G = ndmax <= 4 ? 1 : ndmax <= 8 ? 2 : 4;
+    const int GD = 4 * pl.G;
+    for (int ax = 0; ax < 2; ++ax) pl.ng[ax] = pl.nd[ax] <= 1 ? 1 : (pl.nd[ax] - 1 + GD - 2) / (GD - 1);
+    // §13's split on nb x (groups of both axes) units: from four workgroups per compute unit on, one workgroup walks all lines
+    // of its unit; below that the lines are cut into spans of whole 16-line panels (the longer axis decides how many).
+    const int64_t target = 4 * (int64_t)(cus > 1 ? cus : 1), units = (int64_t)(nb > 1 ? nb : 1) * (pl.ng[0] + pl.ng[1]);
+    const int panels = ((lines[0] > lines[1] ? lines[0] : lines[1]) + 15) / 16;
+    int64_t spans = (target + units - 1) / units;
+    spans = spans < 1 ? 1 : spans > panels ? panels : spans;
+    const int span_panels = (int)((panels + spans - 1) / spans);
+    pl.spans = (panels + span_panels - 1) / span_panels;
+    pl.span_steps = 4 * span_panels;
+    // A stage of about 48 KB, in whole groups of four k-steps (16 map columns on axis 1) where that fits; one k-step of the
+    // widest line (2048 nodes: 129 KB) always does.
+    const size_t step_bytes = (size_t)2 * 4 * ldmax * sizeof(double);
+    int fit = (int)(((size_t)48 << 10) / step_bytes);
+    fit = fit < 1 ? 1 : fit >= 4 ? fit - fit % 4 : fit;
+    pl.stage_steps = fit < pl.span_steps ? fit : pl.span_steps;
+    if (pl.stage_steps > kMtfMapMaxStage) pl.stage_steps = kMtfMapMaxStage;
+    const size_t stage = pl.stage_steps * step_bytes, finish = mtf_finish_doubles(pl.G) * sizeof(double);
+    pl.lds_bytes = stage > finish ? stage : finish;
+    const size_t per_bundle = (size_t)(pl.ng[0] + pl.ng[1]) * pl.spans * GD * kMtfPart * sizeof(double);
+    const size_t fitb = kZfWorkspaceBytes / per_bundle;
+    pl.bundles_per_pass = pl.spans == 1 ? nb : (int)(fitb < 1 ? 1 : fitb > (size_t)nb ? (size_t)nb : fitb);
+    return pl;
+}
+
+// The workgroup's LDS — the stage, the block-range tables, the count — stays within the 160 KB of a gfx950 compute unit at
+// the limits of ort_mtf_map_f64, whatever the split.
+constexpr size_t kMtfMapLdsLimit = (size_t)160 << 10;
+static_assert(mtfmap_plan(1, 2048, 2048, 2048, false, 256).lds_bytes + sizeof(MtfMapShared) <= kMtfMapLdsLimit, "mtf_map: LDS at 2048 x 2048");
+static_assert(mtfmap_plan(1, 2048, 1024, 2048, true, 256).lds_bytes + sizeof(MtfMapShared) <= kMtfMapLdsLimit, "mtf_map: LDS at 2048 x 1024 mirrored");
+static_assert(mtfmap_plan(100000, 2048, 2048, 1, false, 256).lds_bytes + sizeof(MtfMapShared) <= kMtfMapLdsLimit, "mtf_map: LDS, one workgroup per unit");
+static_assert(mtfmap_plan(3, 33, 272, 272, false, 256).ng[0] == 2 && mtfmap_plan(3, 33, 272, 272, false, 256).ng[1] == 1, "mtf_map: groups");
+
+template <int G>
+int mtfmap_launch_accumulate(hipStream_t st, unsigned grid, size_t lds, bool mirror, const MtfMapArgs& a)
+{
+    auto launch = [&](auto kernel) {
+        if (lds + sizeof(MtfMapShared) > ((size_t)64 << 10))
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kMtfBlock), lds, st, a);
+        return (int)ORT_OK;
+    };
+    return mirror ? launch(&k_mtfmap_accumulate<G, true>) : launch(&k_mtfmap_accumulate<G, false>);
+}
+
+// every pointer is a device pointer; count and one of otf, mtf may be null
+int mtfmap_device(ort_ctx* ctx, int nb, int ny, int nx, const double* opd, const double* step, int nshear, double* otf, double* mtf,
+                  int64_t* count, bool mirror)
+{
+    if (nb == 0) return ORT_OK;
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const MtfMapPlan pl = mtfmap_plan(nb, ny, nx, nshear, mirror, cus);
+    const int GD = 4 * pl.G, ngs = pl.ng[0] + pl.ng[1];
+    MtfMapArgs a;
+    a.b0 = 0; a.spans = pl.spans; a.span_steps = pl.span_steps; a.stage_steps = pl.stage_steps;
+    a.ny = ny; a.nx = nx; a.nshear = nshear; a.im_off = 4 * pl.stage_steps * std::max(pl.ld[0], pl.ld[1]);
+    for (int ax = 0; ax < 2; ++ax) { a.nd[ax] = pl.nd[ax]; a.ng[ax] = pl.ng[ax]; a.ld[ax] = pl.ld[ax]; }
+    a.opd = opd; a.step = step; a.ws = nullptr; a.wcnt = nullptr; a.otf = otf; a.mtf = mtf; a.count = count;
+    int rc;
+    if (pl.spans > 1) {
+        rc = dev_out<double>(ctx, SL_MTF_WS, (size_t)pl.bundles_per_pass * ngs * pl.spans * GD * kMtfPart, &a.ws); if (rc) return rc;
+        rc = dev_out<int64_t>(ctx, SL_PSFMAP_CNT, (size_t)pl.bundles_per_pass * ngs * pl.spans, &a.wcnt); if (rc) return rc;
+    }
+    for (int b0 = 0; b0 < nb; b0 += pl.bundles_per_pass) {       // passes share the workspace: stream order keeps them apart
+        const int nbb = std::min(nb - b0, pl.bundles_per_pass);
+        const unsigned units = (unsigned)nbb * (unsigned)ngs, grid = units * (unsigned)pl.spans;
+        a.b0 = b0;
+        switch (pl.G) {
+        case 1: rc = mtfmap_launch_accumulate<1>(ctx->stream, grid, pl.lds_bytes, mirror, a); break;
+        case 2: rc = mtfmap_launch_accumulate<2>(ctx->stream, grid, pl.lds_bytes, mirror, a); break;
+        default: rc = mtfmap_launch_accumulate<4>(ctx->stream, grid, pl.lds_bytes, mirror, a); break;
+        }
+        if (rc) return rc;
+        if (pl.spans > 1) hipLaunchKernelGGL(k_mtfmap_fold, dim3(units), dim3(kMtfBlock), 0, ctx->stream, a, GD, mirror ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    return ORT_OK;
+}
+
 // ---- encircled-energy / GEO radii of spots (k_spot_*, ort_kernels.hpp) ----
 struct SpotPlan {
     char route;              // 'a': slab in LDS; 'b': one workgroup per bundle, q recomputed; 'c': bundles cut into spans
@@ -1848,6 +1951,32 @@ int ort_psf_map_f64(ort_ctx* ctx, int nb, int ny, int nx, const double* opd, con
     rc = psfmap_device(ctx, nb, ny, nx, dopd, dstep, nimg, dxi, dcentre, dpsf, dstrehl, dcount, mirror); if (rc) return rc;
     if (psf) { rc = from_device<double>(ctx, psf, dpsf, (size_t)nb * plane); if (rc) return rc; }
     rc = from_device<double>(ctx, strehl, dstrehl, (size_t)nb); if (rc) return rc;
+    if (count) { rc = from_device<int64_t>(ctx, count, dcount, (size_t)nb); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ORT_OK;
+}
+
+int ort_mtf_map_f64(ort_ctx* ctx, int nb, int ny, int nx, const double* opd, const double* step, int nshear, double* otf, double* mtf,
+                    int64_t* count, unsigned flags)
+{
+    int rc = check_ctx(ctx); if (rc) return rc;
+    const bool mirror = (flags & ORT_MAP_MIRROR_X) != 0;
+    if (nb < 0 || !opd || !step || (!otf && !mtf)) return fail(ORT_EINVAL, "bad mtf_map arguments");
+    if (ny < 1 || ny > kMtfMapMaxN || nx < 1 || nx > kMtfMapMaxN) return fail(ORT_EINVAL, "mtf_map: map %d x %d outside 1..%d", ny, nx, kMtfMapMaxN);
+    if (mirror && nx > kMtfMapMaxN / 2) return fail(ORT_EINVAL, "mtf_map: mirrored nx %d above %d", nx, kMtfMapMaxN / 2);
+    if (nshear < 1 || nshear > kMtfMapMaxN) return fail(ORT_EINVAL, "mtf_map: nshear %d outside 1..%d", nshear, kMtfMapMaxN);
+    if (nb == 0) return ORT_OK;
+    if ((flags & ORT_DEVICE_PTRS)) return mtfmap_device(ctx, nb, ny, nx, opd, step, nshear, otf, mtf, count, mirror);
+    const size_t curves = (size_t)nb * 2 * (size_t)nshear;
+    const double *dopd, *dstep; double *dotf = nullptr, *dmtf = nullptr; int64_t* dcount = nullptr;
+    rc = to_device<double>(ctx, SL_IN0, opd, (size_t)nb * ny * nx, &dopd); if (rc) return rc;
+    rc = to_device<double>(ctx, SL_IN1, step, (size_t)nb * 2, &dstep); if (rc) return rc;
+    if (otf) { rc = dev_out<double>(ctx, SL_OUT0, 2 * curves, &dotf); if (rc) return rc; }
+    if (mtf) { rc = dev_out<double>(ctx, SL_OUT1, curves, &dmtf); if (rc) return rc; }
+    if (count) { rc = dev_out<int64_t>(ctx, SL_OUT2, (size_t)nb, &dcount); if (rc) return rc; }
+    rc = mtfmap_device(ctx, nb, ny, nx, dopd, dstep, nshear, dotf, dmtf, dcount, mirror); if (rc) return rc;
+    if (otf) { rc = from_device<double>(ctx, otf, dotf, 2 * curves); if (rc) return rc; }
+    if (mtf) { rc = from_device<double>(ctx, mtf, dmtf, curves); if (rc) return rc; }
     if (count) { rc = from_device<int64_t>(ctx, count, dcount, (size_t)nb); if (rc) return rc; }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ORT_OK;

@@ -4451,6 +4451,212 @@ __global__ ORT_ZF_FN __launch_bounds__(kPsfBlock) void k_psfmap_strehl(PsfMapArg
     }
 }
 
+
+// ------------------------------------------------------------------------------------
+// Sagittal and tangential OTF / MTF of sampled wavefronts — OPD maps — on the device (ort_mtf_map_f64, include/ort.h).
+//
+// The autocorrelation of k_mtf_* with the pupil field of k_psfmap_*: P[j][k] = exp(i 2 pi W[j][k]) on the nodes that are not
+// NaN, 0 elsewhere.  Per axis the map is a set of LINES (the sum index) of a WIDTH (the shear index):
+//     axis 0   lines = map rows j,     width = nx (2 nx - 1 mirrored)     N H_0(d) = sum_j sum_k P[j][k + d] conj(P[j][k])
+//     axis 1   lines = map columns k,  width = ny                         N H_1(d) = sum_k sum_j P[j + d][k] conj(P[j][k])
+// and N H(d) is the sum of the d-th sub-diagonal of the Gram matrix of the lines, as in k_mtf_*: one complex accumulator tile
+// per block diagonal, four matrix instructions per (diagonal, J), the same LDS register as A operand of block row I and B
+// operand of block column J, waves dealt diagonals back and forth, groups of 4 G tiles overlapping by one, offset sums
+// through a 4 KB scratch per wave, and the finish "tile D for r >= c, tile D + 1 for r < c".  What a map changes:
+//
+//   stage      a stage of k-steps of 4 lines is LOADED: one load and one sincospi(2 W) per node; NaN nodes and the padding to
+//              16 in width and 4 in lines give 0; the contributing count is taken in the same pass, as an integer.
+//              axis 0: consecutive lanes take consecutive nodes of a map row.  MIRROR: position k' of the full row reads map
+//              column |k' - (nx - 1)|, so the row of 2 nx - 1 nodes stands in LDS as if the map were explicit.
+//              axis 1: consecutive lanes take the stage's consecutive map columns of one map row (16 columns = one 128-byte
+//              segment when the stage holds four k-steps) and store them transposed, line stride odd.  MIRROR: the half
+//              map is walked once and line k >= 1 carries weight 2 on the J operand, a per-lane constant of the k-step.
+//   clipping   while a stage is built every contributing node lowers lo / raises hi of its k-step's block range (integer LDS
+//              atomics behind a plain compare); after the stage's barrier the range is uniform and the J walk runs
+//              lo <= J, J + D <= hi.  An empty or too narrow k-step issues nothing.  Zeros contribute zero: speed only.
+//   diagonals  only nd = min(ceil(width / 16), ceil(nshear / 16) + 1) tiles per axis are accumulated, and the groups are
+//              formed from nd; the axes may have different group counts, a unit is (bundle, axis, group of ITS axis).
+//   finish     N is known after the walk: the one-workgroup route reduces its integer count, divides, negates Im for a
+//              negative step of the axis (the shear is a physical displacement) and writes; samples at or past the width
+//              are +0.  The last group of an axis also writes the samples past the axis's last tile.  Spans store their
+//              offset sums and their count plainly; k_mtfmap_fold adds both in span order and does the same finish.
+//              count[b] is written by the unit (axis 0, group 0).
+//
+//   k_mtfmap_accumulate<G, MIRROR>   grid: bundles of the pass x (groups of axis 0 + groups of axis 1) x spans
+//   k_mtfmap_fold                    grid: bundles of the pass x (groups of axis 0 + groups of axis 1)
+// ------------------------------------------------------------------------------------
+constexpr int kMtfMapMaxN = 2048;             // ny, nx, nshear <= 2048; the mirrored nx <= 1024: a full row is one LDS line
+constexpr int kMtfMapMaxStage = 64;           // k-steps per LDS stage at most: the size of the block-range tables
+
+struct MtfMapArgs {
+    int b0, spans, span_steps, stage_steps;   // k-steps of 4 lines per span and per LDS stage
+    int ny, nx, nshear, im_off;               // im_off: doubles between the stage's real and imaginary plane
+    int nd[2], ng[2], ld[2];                  // per axis: tiles accumulated, groups, LDS line stride in doubles
+    const double* opd;                        // [nb][ny][nx]
+    const double* step;                       // [nb][2] = {dpy, dpx}
+    double* ws;                               // [bundle of the pass][axis, group][span][4 G][31][2]
+    int64_t* wcnt;                            // [bundle of the pass][axis, group][span]
+    double *otf, *mtf;                        // [nb][2][nshear][2] or null, [nb][2][nshear] or null
+    int64_t* count;                           // [nb] or null
+};
+
+struct MtfMapShared {
+    int cnt[4];
+    int lo[2][kMtfMapMaxStage], hi[2][kMtfMapMaxStage];          // [stage parity][k-step]: first and last non-zero block;
+};                                                               // empty: lo = 1 << 20 (J + D cannot overflow), hi = -1
+
+// Thread tid's sample of the unit (bundle b, axis, group g) from the offset sums of `parts` slots of stride `stride`, added in
+// slot order, with N contributing nodes; then the samples no tile reaches, and the bundle's count.
+ORT_ZF_FN __device__ __forceinline__ void mtfmap_finish(const MtfMapArgs& a, int GD, bool mirror, int b, int axis, int g, int64_t N,
+                                                        const double* part, int parts, size_t stride, int tid)
+{
+    const double dpy = a.step[2 * (size_t)b], dpx = a.step[2 * (size_t)b + 1], dp = axis ? dpy : dpx;
+    const bool ok = dpy != 0.0 && dpx != 0.0 && fabs(dpy) < __builtin_inf() && fabs(dpx) < __builtin_inf() && N > 0;
+    const int width = axis ? a.ny : (mirror ? 2 * a.nx - 1 : a.nx), nd = a.nd[axis], nshear = a.nshear;
+    const int t = tid >> 4, m = tid & 15, D0 = g * (GD - 1), D = D0 + t, d = 16 * D + m;
+    const double nan = __builtin_nan("");
+    const size_t o0 = ((size_t)b * 2 + axis) * nshear;
+    if (t < GD && D < nd && d < nshear && !(t == GD - 1 && D0 + GD < nd)) {      // (the next group writes its first block)
+        double re = 0.0, im = 0.0;
+        for (int s = 0; s < parts; ++s) {
+            const double* q = part + s * stride;
+            re += q[(t * kMtfOffsets + 15 + m) * 2]; im += q[(t * kMtfOffsets + 15 + m) * 2 + 1];
+            if (m > 0 && t + 1 < GD) { re += q[((t + 1) * kMtfOffsets + m - 1) * 2]; im += q[((t + 1) * kMtfOffsets + m - 1) * 2 + 1]; }
+        }
+        re = re / (double)N; im = im / (double)N;
+        if (dp < 0.0) im = -im;                                  // index shear d = physical shear -d |dp|: the conjugate
+        if (d >= width) { re = 0.0; im = 0.0; }
+        if (!ok) { re = nan; im = nan; }
+        if (a.otf) { a.otf[2 * (o0 + d)] = re; a.otf[2 * (o0 + d) + 1] = im; }
+        if (a.mtf) a.mtf[o0 + d] = ok ? mtf_hypot(re, im) : nan;
+    }
+    if (D0 + GD >= nd)                                           // the axis's last group: no tile reaches these samples
+        for (int e = 16 * nd + tid; e < nshear; e += kMtfBlock) {
+            const double z = ok ? 0.0 : nan;
+            if (a.otf) { a.otf[2 * (o0 + e)] = z; a.otf[2 * (o0 + e) + 1] = z; }
+            if (a.mtf) a.mtf[o0 + e] = z;
+        }
+    if (axis == 0 && g == 0 && tid == 0 && a.count) a.count[b] = N;
+}
+
+// Dynamic LDS: max(2 x 4 stage_steps x max(ld), mtf_finish_doubles(G)) doubles, through mtf_lds.
+template <int G, bool MIRROR>
+__global__ ORT_ZF_FN __launch_bounds__(kMtfBlock) void k_mtfmap_accumulate(MtfMapArgs a)
+{
+    constexpr int GD = 4 * G;
+    __shared__ MtfMapShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int u = blockIdx.x;
+    const int span = u % a.spans; u /= a.spans;
+    const int ngs = a.ng[0] + a.ng[1], r = u % ngs, bl = u / ngs, b = a.b0 + bl;
+    const int axis = r >= a.ng[0] ? 1 : 0, g = r - (axis ? a.ng[0] : 0);
+    const int ny = a.ny, nx = a.nx;
+    const int lines = axis ? nx : ny, width = axis ? ny : (MIRROR ? 2 * nx - 1 : nx);
+    const int wpad = 16 * ((width + 15) / 16), nd = a.nd[axis], ld = a.ld[axis], D0 = g * (GD - 1);
+    const int nsteps = (lines + 3) / 4, s_lo = min(span * a.span_steps, nsteps), s_hi = min(s_lo + a.span_steps, nsteps);
+    const double* map = a.opd + (size_t)b * ny * nx;
+    double* re = mtf_lds;
+    double* im = mtf_lds + a.im_off;
+    if (tid < kMtfMapMaxStage) { sh.lo[0][tid] = 1 << 20; sh.hi[0][tid] = -1; }
+    int dq[G];                                                   // this wave's diagonals, relative to J
+#pragma unroll
+    for (int q = 0; q < G; ++q) dq[q] = D0 + 4 * q + ((q & 1) ? 3 - wave : wave);
+    const bool idle = dq[0] >= nd;                               // none of this wave's tiles is asked for (uniform)
+    zf_d4 Ar[G], Ai[G];
+#pragma unroll
+    for (int q = 0; q < G; ++q) { Ar[q] = zf_d4{0.0, 0.0, 0.0, 0.0}; Ai[q] = zf_d4{0.0, 0.0, 0.0, 0.0}; }
+    int n = 0, par = 0;                                          // this thread's weighted node count; the stage's parity
+    for (int s0 = s_lo; s0 < s_hi; s0 += a.stage_steps, par ^= 1) {
+        const int ns = min(a.stage_steps, s_hi - s0), l0 = 4 * s0, nl = 4 * ns;
+        __syncthreads();                                         // the previous stage's readers are done
+        if (tid < kMtfMapMaxStage) { sh.lo[par ^ 1][tid] = 1 << 20; sh.hi[par ^ 1][tid] = -1; }
+        volatile int* lo = sh.lo[par];
+        volatile int* hi = sh.hi[par];
+        for (int e = tid; e < nl * wpad; e += kMtfBlock) {
+            int rl, k, j, c;                                     // line of the stage, position along it; the map's row, column
+            bool in;
+            if (axis == 0) {
+                rl = e / wpad; k = e - rl * wpad;
+                j = l0 + rl; c = MIRROR ? abs(k - (nx - 1)) : k; in = j < ny && k < width;
+            } else {
+                k = e / nl; rl = e - k * nl;
+                j = k; c = l0 + rl; in = c < nx && j < ny;
+            }
+            double pr = 0.0, pi = 0.0;
+            if (in) {
+                const double W = map[(size_t)j * nx + c];
+                if (W == W) {
+                    sincospi(2.0 * W, &pi, &pr);
+                    n += (MIRROR && axis == 1 && c > 0) ? 2 : 1;
+                    const int ks = rl >> 2, blk = k >> 4;
+                    if (blk < lo[ks]) atomicMin(&sh.lo[par][ks], blk);
+                    if (blk > hi[ks]) atomicMax(&sh.hi[par][ks], blk);
+                }
+            }
+            re[rl * ld + k] = pr; im[rl * ld + k] = pi;
+        }
+        __syncthreads();
+        if (idle) continue;
+        for (int ks = 0; ks < ns; ++ks) {
+            const int lo_k = __builtin_amdgcn_readfirstlane(lo[ks]), hi_k = __builtin_amdgcn_readfirstlane(hi[ks]);
+            const int row = 4 * ks + (lane >> 4);
+            const double* rr = re + row * ld + (lane & 15);
+            const double* ri = im + row * ld + (lane & 15);
+            const double wJ = (MIRROR && axis == 1 && l0 + row > 0) ? 2.0 : 1.0;      // the mirrored twin of this lane's line
+            for (int J = lo_k; J + dq[0] <= hi_k; ++J) {         // dq[0] is the wave's smallest
+                double cJ = rr[16 * J], sJ = ri[16 * J];
+                if constexpr (MIRROR) { cJ *= wJ; sJ *= wJ; }
+                const double nsJ = -sJ;
+#pragma unroll
+                for (int q = 0; q < G; ++q) {
+                    const int I = J + dq[q];
+                    if (I > hi_k || dq[q] >= nd) continue;       // uniform over the wave
+                    const double cI = rr[16 * I], sI = ri[16 * I];
+                    Ar[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cI, cJ, Ar[q], 0, 0, 0);
+                    Ar[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(sI, sJ, Ar[q], 0, 0, 0);
+                    Ai[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(sI, cJ, Ai[q], 0, 0, 0);
+                    Ai[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(cI, nsJ, Ai[q], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // Offset sums, as in k_mtf_accumulate.  Element (r, c) of a tile is register r / 4 of lane 16 (r % 4) + c (zf_tile_offset).
+    double* scratch = mtf_lds + wave * 512;
+    double* part = mtf_lds + 4 * 512;
+#pragma unroll
+    for (int q = 0; q < G; ++q) {
+        __syncthreads();                                         // the stage's, then the previous tile's readers are done
+#pragma unroll
+        for (int v = 0; v < 4; ++v) { scratch[v * 64 + lane] = Ar[q][v]; scratch[256 + v * 64 + lane] = Ai[q][v]; }
+        __syncthreads();
+        if (lane < kMtfPart) {
+            const int o = lane >> 1, off = o - 15;
+            const double* src = scratch + (lane & 1) * 256;
+            double s = 0.0;
+            for (int c = off < 0 ? -off : 0; c <= (off > 0 ? 15 - off : 15); ++c) s += src[zf_tile_offset(c + off, c)];
+            part[(dq[q] - D0) * kMtfPart + lane] = s;
+        }
+    }
+    const int N = psfmap_count(n, sh.cnt, tid);                  // its barrier also publishes the offset sums
+    if (a.spans == 1) mtfmap_finish(a, GD, MIRROR, b, axis, g, N, part, 1, 0, tid);
+    else {
+        double* slot = a.ws + (size_t)blockIdx.x * (GD * kMtfPart);
+        for (int e = tid; e < GD * kMtfPart; e += kMtfBlock) slot[e] = part[e];
+        if (tid == 0) a.wcnt[blockIdx.x] = N;
+    }
+}
+
+// Grid: bundles of the pass x (groups of axis 0 + groups of axis 1); one thread per sample.
+__global__ ORT_ZF_FN __launch_bounds__(kMtfBlock) void k_mtfmap_fold(MtfMapArgs a, int GD, int mirror)
+{
+    const int ngs = a.ng[0] + a.ng[1], r = blockIdx.x % ngs, b = a.b0 + blockIdx.x / ngs;
+    const int axis = r >= a.ng[0] ? 1 : 0, g = r - (axis ? a.ng[0] : 0);
+    int64_t N = 0;
+    for (int s = 0; s < a.spans; ++s) N += a.wcnt[(size_t)blockIdx.x * a.spans + s];
+    const size_t stride = (size_t)GD * kMtfPart;
+    mtfmap_finish(a, GD, mirror != 0, b, axis, g, N, a.ws + (size_t)blockIdx.x * a.spans * stride, a.spans, stride, threadIdx.x);
+}
+
 #undef ORT_ZF_FN
 
 }  // namespace ort

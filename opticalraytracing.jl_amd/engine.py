@@ -354,6 +354,36 @@ class HipEngine:
             otf = torch.view_as_complex(otf) if hasattr(otf, "data_ptr") else otf.view(np.complex128)[..., 0]
         return mtf, otf
 
+    # ---- sagittal / tangential OTF and MTF of OPD maps ----
+    def mtf_map(self, opd, step, nshear: int, mirror_x: bool = False, want_otf: bool = False):
+        """`ort_mtf_map_f64`: the modulus transfer function [nb][2][nshear] of the sampled wavefronts opd [nb][ny][nx] (waves,
+        NaN = node outside the pupil: the maps of `opd_grid`) with step [nb][2] = (dpy, dpx) as for `psf_map` — the
+        autocorrelation of the map's pupil field along x (axis 0, sample d at d |dpx| cycles per wavegrad unit) and along y
+        (axis 1, d |dpy|); samples at or past the width of an axis are 0.  mirror_x: the maps are the x >= 0 half of a pupil
+        symmetric about x = 0.  Returns (mtf, otf or None, count); want_otf = True also gives the complex OTF [nb][2][nshear]
+        (complex128); count [nb] is the number of contributing nodes, and a bundle without any, or with a zero or non-finite
+        step, gives NaN.  numpy arrays go through host buffers; torch CUDA tensors (opd, step) stay on the device — the call
+        is asynchronous on the engine's stream and the results are torch tensors."""
+        nb, ny, nx = opd.shape
+        if hasattr(opd, "data_ptr"):
+            import torch
+            otf = torch.empty((nb, 2, nshear, 2), dtype=torch.float64, device=opd.device) if want_otf else None
+            mtf = torch.empty((nb, 2, nshear), dtype=torch.float64, device=opd.device)
+            count = torch.empty(nb, dtype=torch.int64, device=opd.device)
+            flags = self.base_flags | _capi.ORT_DEVICE_PTRS
+        else:
+            opd, step = f64(opd), f64(step)
+            otf = np.empty((nb, 2, nshear, 2)) if want_otf else None
+            mtf, count = np.empty((nb, 2, nshear)), np.empty(nb, dtype=np.int64)
+            flags = self.base_flags
+        if mirror_x:
+            flags |= _capi.ORT_MAP_MIRROR_X
+        check(self.ctx.lib.ort_mtf_map_f64(self.ctx.h, int(nb), int(ny), int(nx), ptr(opd), ptr(step), int(nshear),
+                                           None if otf is None else ptr(otf), ptr(mtf), ptr(count), flags))
+        if otf is not None:
+            otf = torch.view_as_complex(otf) if hasattr(otf, "data_ptr") else otf.view(np.complex128)[..., 0]
+        return mtf, otf, count
+
     # ---- GEO / encircled-energy radii of full_trace results ----
     def spot_radii(self, ex, ey, count, fractions=(0.5, 0.8, 1.0)):
         """`ort_spot_radii_f64` / `_f32` (by the dtype of ex): for nb full_trace slabs [nb][cap] with count[b] valid entries,
